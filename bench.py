@@ -6,6 +6,14 @@ whole synthetic graph, inputs resident in HBM, CSR plan already built (it is cac
 adjacency, main.py:495 passes the same tensor every batch). Edges/s = K * nnz(Â) / t_step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--gen powerlaw|uniform]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --dump-outputs DIR
+also writes the last timed step's output (a seeded row sample of it) as DIR/*.npy; the inputs are
+seeded, so two builds can be compared output for output. --full adds everything else to the
+line: roofline and per-kernel timing, the device adjacency builder, C4 on the same graph,
+backward, evaluation, the training step, the CPU baseline with parity, chunk mode and the
+trained Recall@20 (minutes of CPU and GPU work).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the adjacency is row-partitioned by
 nnz, each rank owns a slice of rows, and every layer all-gathers the embedding slices over RCCL
@@ -16,6 +24,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 # The bipartite two-lane schedule runs 8 streams (lgcn_sched_create: the caller's + 7). HIP keeps
 # GPU_MAX_HW_QUEUES hardware queues (default 4) per stream priority, and the second lane's four
@@ -119,6 +128,30 @@ def make_graph(cfg, gen, heldout_users, keep_interactions=False):
 def xavier(rows, d, gen):
     bound = float(np.sqrt(6.0 / (rows + d)))
     return (torch.rand(rows, d, generator=gen) * 2 - 1) * bound
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: cap of the dumped table (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, out, r, hub_thr):
+    """--dump-outputs: the final embeddings the timed path returned in its last timed step, as
+    path/final_embeddings.npy (float32). A table above DUMP_BYTES is sampled by rows: the rows
+    above the hub threshold (the exact plan's emulated and chained rows; at most a quarter of the
+    sample) and a seeded draw over all rows, in row order — the same rows for the same arguments.
+    path/final_embeddings_rows.npy (float64) holds their indices."""
+    n, d = out.shape
+    cap = DUMP_BYTES // (4 * d)
+    if n > cap:
+        hubs = np.nonzero(np.bincount(r, minlength=n) > hub_thr)[0][:cap // 4]
+        draw = np.random.default_rng(11).choice(n, cap - hubs.size, replace=False)
+        rows = np.union1d(hubs, draw)
+        table = out[torch.from_numpy(rows).to(out.device)]
+    else:
+        rows, table = np.arange(n), out
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "final_embeddings.npy"), table.cpu().numpy())
+    np.save(os.path.join(path, "final_embeddings_rows.npy"), rows.astype(np.float64))
+    log(f"[bench] dumped {rows.size:,} of {n:,} output rows to {path}")
 
 
 def bench_eval(final, U, I, r, c, dev, args, n_users=8192, k=20):
@@ -490,13 +523,24 @@ def main():
                     help="N > 1: skip the secondary rowpart (per-layer RCCL all-gather) timing")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the distributed path even at WORLD_SIZE=1 (testing)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline, also measure and check everything else "
+                         "(roofline and per-kernel timing, adjacency builder, C4, backward, eval, "
+                         "training step, CPU baseline + parity, chunk mode, trained Recall@20)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: write the last timed step's output to DIR/*.npy (float32 "
+                         "table, a seeded row sample when it is above 32 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     # LGCN_SHARED_GPU=1 (with LGCN_DIST_BACKEND=gloo): every rank on cuda:0 — a rehearsal of
     # the N > 1 path on a one-GPU box; the numbers it prints are not a scaling measurement
     local_rank = 0 if os.environ.get("LGCN_SHARED_GPU") else int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (world > 1 or args.force_dist):
+        ap.error("--dump-outputs writes the one-GPU run's output")
     if world != args.gpus:
         log(f"[bench] note: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE")
     cfg = CONFIGS[args.config]
@@ -506,13 +550,19 @@ def main():
     engine.load_library()
     hub_thr = args.hub_threshold if args.hub_threshold is not None else engine.hub_threshold_from_env()
 
-    r, c, v, ev_users, ev_items, inter = make_graph(cfg, args.gen, args.recall_users,
-                                                    keep_interactions=(world == 1))
     U, I, B = cfg["users"], cfg["items"], cfg.get("brands", 0)
+
+    def tables():
+        gen = torch.Generator().manual_seed(42)
+        return [xavier(U, d, gen), xavier(I, d, gen)] + ([xavier(B, d, gen)] if B else [])
+    # the tables (a serial generator) are drawn beside the graph build: both release the GIL
+    with ThreadPoolExecutor(1) as pool:
+        emb_job = pool.submit(tables)
+        r, c, v, ev_users, ev_items, inter = make_graph(
+            cfg, args.gen, args.recall_users, keep_interactions=(world == 1 and args.full))
+        emb_host = emb_job.result()
     n = U + I + B
     nnz = len(v)
-    gen = torch.Generator().manual_seed(42)
-    emb_host = [xavier(U, d, gen), xavier(I, d, gen)] + ([xavier(B, d, gen)] if B else [])
     fusion = cfg.get("content", 0)
 
     if world > 1 or args.force_dist:
@@ -537,17 +587,6 @@ def main():
     torch.cuda.synchronize()
     prep_s = time.time() - t0
     segs = [t.to(dev) for t in emb_host]
-    # the device adjacency builder (SURVEY §8f row 2) on the same interactions: time + bitwise
-    u_, i_, ib_, t_norm = inter
-    torch.cuda.synchronize()
-    t0 = time.time()
-    adj_dev = graph.build_norm_adj_device(u_, i_, U, I, B, ib_[0], ib_[1], bool(B), device=dev)
-    torch.cuda.synchronize()
-    t_dev = time.time() - t0
-    builder = {"host_numpy_s": round(t_norm, 2), "device_s": round(t_dev, 2),
-               "bitwise_equal": bool(torch.equal(adj_dev._indices(), adj._indices()) and torch.equal(
-                   adj_dev._values().view(torch.int32), adj._values().view(torch.int32)))}
-    del adj_dev, inter, u_, i_
     if hp.mode == "exact":
         log(f"[bench] CSR plan {prep_s:.2f}s; exact plan: {hp.n_emu_rows} rows above the "
             f"threshold {hub_thr} ({hp.n_emu_blocks} emulation blocks; the shorter ones run as "
@@ -581,29 +620,33 @@ def main():
             b_.record()
             torch.cuda.synchronize()
             return a_.elapsed_time(b_) / reps
-        with torch.no_grad():
-            t_fused = prelayer_ms(lambda: FU.fused_item_embedding(segs[1], content, lin))
-            t_torch = prelayer_ms(lambda: torch.nn.functional.leaky_relu(
-                lin(torch.cat([segs[1], content], 1))))
-            f_ref = torch.nn.functional.leaky_relu(lin(torch.cat([segs[1], content], 1)))
-            f_got = FU.fused_item_embedding(segs[1], content, lin)
-            pre_err = float((f_got - f_ref).abs().max() / f_ref.abs().max())
-        fl = 2.0 * I * (d + fusion) * d
-        prelayer = {"fused_ms": round(t_fused, 3), "torch_ops_ms": round(t_torch, 3),
+
+        def bench_prelayer():
+            with torch.no_grad():
+                t_fused = prelayer_ms(lambda: FU.fused_item_embedding(segs[1], content, lin))
+                t_torch = prelayer_ms(lambda: torch.nn.functional.leaky_relu(
+                    lin(torch.cat([segs[1], content], 1))))
+                f_ref = torch.nn.functional.leaky_relu(lin(torch.cat([segs[1], content], 1)))
+                f_got = FU.fused_item_embedding(segs[1], content, lin)
+                pre_err = float((f_got - f_ref).abs().max() / f_ref.abs().max())
+            fl = 2.0 * I * (d + fusion) * d
+            return {"fused_ms": round(t_fused, 3), "torch_ops_ms": round(t_torch, 3),
                     "fused_tflops": round(fl / (t_fused / 1e3) / 1e12, 1),
                     "normwise_vs_torch": pre_err,
                     "what": "lightgcn_fusion.py:45-49 leaky_relu(Linear(cat([id, content]))): "
                             "lgcn_fusion_prelayer vs torch cat + Linear (hipBLASLt) + leaky_relu"}
+        prelayer = bench_prelayer() if args.full else None
     else:
         def step(ev=None, kev=None, mode=None):
             return engine.propagate_forward(g, segs, K, hub_thr, layer_events=ev,
                                             kernel_events=kev, hub_mode=mode)
 
-    def timed(mode, steps, warmup):
+    def timed(mode, steps, warmup, kernels=True):
         """(ms per step, [steps x K] layer ms, [steps x K] layer-kernel ms, output). Sided: no
         layer boundary exists (the two lanes overlap layers), layer ms is None and the kernel ms
         are [steps x K x 4] — each segment's layer kernel (the side-0 classes, side 1), timed on
-        its lane's stream (0 for an empty segment)."""
+        its lane's stream (0 for an empty segment); they take a second loop of the same steps,
+        which runs only with `kernels` (else they are None)."""
         for _ in range(warmup):
             step(mode=mode)
         torch.cuda.synchronize()
@@ -617,6 +660,8 @@ def main():
             o = step(None, None, mode) if sided else step(evs[s_], kevs[s_], mode)
         b_.record()
         torch.cuda.synchronize()
+        if sided and not kernels:
+            return a_.elapsed_time(b_) / steps, None, None, o
         if sided:
             # the half-layers' layer-kernel times from a second loop of the same steps: the
             # timing events recorded on the lanes' streams cost the timed loop ~0.5 ms per step
@@ -650,10 +695,46 @@ def main():
     hub_mode = engine.hub_mode_from_env()
     torch.cuda.synchronize()
     t_wall = time.time()
-    ms_step, layer_ms, kern_ms, out = timed(hub_mode, args.steps, args.warmup)
+    ms_step, layer_ms, kern_ms, out = timed(hub_mode, args.steps, args.warmup, kernels=args.full)
     wall = time.time() - t_wall
     ms_total = ms_step * args.steps
     value = K * nnz * args.steps / (ms_total / 1e3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, r, hub_thr)
+
+    result = {
+        "metric": "propagated edges/sec (SpMM) + Recall@20, Amazon-Books 3-layer d=64",
+        "value": round(value, 1), "unit": "edges/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": cfg["name"], "generator": args.gen, "users": U, "items": I,
+                   "interactions": cfg["interactions"], "nnz": nnz, "d": d, "layers": K,
+                   "brands": B, "content_dim": fusion,
+                   "hub_threshold": hub_thr, "hub_mode": hub_mode,
+                   "emu_min_degree": engine.emu_min_degree_from_env(nnz),
+                   "schedule": ("bipartite two-lane (lgcn_propagate_forward_sides), "
+                                f"side-0 classes {list(g.class_end or ())} (parts "
+                                f"{list(g.class_parts)}), "
+                                f"{engine.n_aux_streams()} aux streams, GPU_MAX_HW_QUEUES="
+                                f"{os.environ.get('GPU_MAX_HW_QUEUES', 'unset (HIP default 4)')}") if sided else "one operator",
+                   "parallelism": "single"},
+        "wall_s_timed": round(wall, 3), "prep_s": round(prep_s, 2),
+    }
+    if not args.full:  # the headline alone; everything below is --full
+        print(json.dumps(result), flush=True)
+        return
+
+    # the device adjacency builder (SURVEY §8f row 2) on the same interactions: time + bitwise
+    u_, i_, ib_, t_norm = inter
+    torch.cuda.synchronize()
+    t0 = time.time()
+    adj_dev = graph.build_norm_adj_device(u_, i_, U, I, B, ib_[0], ib_[1], bool(B), device=dev)
+    torch.cuda.synchronize()
+    t_dev = time.time() - t0
+    builder = {"host_numpy_s": round(t_norm, 2), "device_s": round(t_dev, 2),
+               "bitwise_equal": bool(torch.equal(adj_dev._indices(), adj._indices()) and torch.equal(
+                   adj_dev._values().view(torch.int32), adj._values().view(torch.int32)))}
+    del adj_dev, inter, u_, i_
 
     # Roofline of the dominant HBM kernel: the STORE instantiation of k_layer (layers
     # 1..K-1; rocprof name k_layer<float4,16,1,0,15,4,0,0>), timed live with HIP events around
@@ -765,26 +846,8 @@ def main():
             roof["kernels_measured"] = ks
     attach_traffic(roof, hub_mode, store_ms)
 
-    result = {
-        "metric": "propagated edges/sec (SpMM) + Recall@20, Amazon-Books 3-layer d=64",
-        "value": round(value, 1), "unit": "edges/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": cfg["name"], "generator": args.gen, "users": U, "items": I,
-                   "interactions": cfg["interactions"], "nnz": nnz, "d": d, "layers": K,
-                   "brands": B, "content_dim": fusion,
-                   "hub_threshold": hub_thr, "hub_mode": hub_mode,
-                   "emu_min_degree": engine.emu_min_degree_from_env(nnz),
-                   "schedule": ("bipartite two-lane (lgcn_propagate_forward_sides), "
-                                f"side-0 classes {list(g.class_end or ())} (parts "
-                                f"{list(g.class_parts)}), "
-                                f"{engine.n_aux_streams()} aux streams, GPU_MAX_HW_QUEUES="
-                                f"{os.environ.get('GPU_MAX_HW_QUEUES', 'unset (HIP default 4)')}") if sided else "one operator",
-                   "parallelism": "single"},
-        "roofline": roof,
-        "wall_s_timed": round(wall, 3), "prep_s": round(prep_s, 2),
-        "adjacency_build": builder,
-    }
+    result["roofline"] = roof
+    result["adjacency_build"] = builder
     if fusion:
         result["fusion_prelayer"] = prelayer
     if sided:

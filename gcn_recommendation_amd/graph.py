@@ -6,6 +6,9 @@ synthetic interaction generators for BASELINE.json's configs.
 scales to the Books-size graphs. Checked against the reference-built Â in
 tests/test_graph_builder.py (golden fixtures).
 """
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import torch
 
@@ -30,7 +33,7 @@ def normalise(rows, cols, n):
         dinv = np.power(rowsum, np.float32(-0.5))
     dinv[np.isinf(dinv)] = np.float32(0.0)
     key = rows * np.int64(n) + cols
-    key.sort(kind="stable")
+    key.sort()  # integer keys: equal keys are indistinguishable, any sort gives the stable result
     if key.size:
         start = np.concatenate([[True], key[1:] != key[:-1]])
         ukey = key[start]
@@ -133,7 +136,16 @@ def _zipf_draw(rng, n_cat, alpha, size):
     w = np.power(np.arange(1, n_cat + 1, dtype=np.float64), -alpha)
     cdf = np.cumsum(w)
     cdf /= cdf[-1]
-    ranks = np.searchsorted(cdf, rng.random(size), side="right")
+    # the binary searches miss the cache at Books size; numpy releases the GIL in searchsorted,
+    # so slices of the draws run on a few threads (the same ranks, ~8x sooner)
+    x = rng.random(size)
+    ranks = np.empty(size, np.int64)
+    step = 1 << 18
+
+    def search(s):
+        ranks[s:s + step] = np.searchsorted(cdf, x[s:s + step], side="right")
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
+        list(pool.map(search, range(0, size, step)))
     ranks = np.minimum(ranks, n_cat - 1)
     perm = rng.permutation(n_cat)
     return perm[ranks]

@@ -59,12 +59,28 @@ def test_ctor_errors():
     assert m.item_embedding.weight.requires_grad
 
 
+def _assert_matches_fixture(got, z, key, behind_gemm):
+    """Bitwise the fixture's tensor (its sha1). A tensor computed through the fusion Linear's dense
+    GEMMs may differ where the BLAS library picks another kernel for the host CPU (another
+    summation order): that one must still meet the project's parity gate against the stored
+    values (all of them, or the first rows), 1e-5 of the whole tensor's max |value|."""
+    if sha1(got) == str(z["sha1/" + key]):
+        return
+    assert behind_gemm, key
+    want = z["full/" + key] if "full/" + key in z.files else z["head/" + key]
+    err = float(np.abs(got[:len(want)].astype(np.float64) - want).max())
+    assert err <= 1e-5 * float(z["absmax/" + key]), (key, err)
+
+
 @pytest.mark.parametrize("name", CASES + ["c1_fusion"])
 def test_cpu_forward_backward_match_reference(name):
     """CPU adjacency (BASELINE configs[0], plumbing): bitwise = the reference's outputs.
     (Fixtures were generated single-threaded; MKL's GEMM in the fusion Linear is thread-count
-    dependent, so run single-threaded here too.)"""
+    dependent, so run single-threaded here too. Its kernel, and so its summation order, also
+    depends on the host CPU: what the fusion case computes through the Linear is bitwise or
+    within the parity gate, everything else is bitwise.)"""
     torch.set_num_threads(1)
+    fusion = name == "c1_fusion"
     z = load_case(name)
     U, I, B, d, K = case_dims(z)
     m = _make(name, z)
@@ -75,11 +91,13 @@ def test_cpu_forward_backward_match_reference(name):
     fu, fi, fb, u0, i0 = out
     assert fu.shape == (U, d) and fi.shape == (I, d) and fb.shape == (B, d)
     assert u0 is m.user_embedding.weight
-    assert sha1(torch.cat([fu, fi, fb]).detach().numpy()) == str(z["sha1/final"])
+    _assert_matches_fixture(torch.cat([fu, fi, fb]).detach().numpy(), z, "final", fusion)
     G = torch.from_numpy(np.random.default_rng(7).standard_normal((U + I + B, d)).astype(np.float32))
     (torch.cat([fu, fi, fb]) * G).sum().backward()
     for n, p in m.named_parameters():
-        assert sha1(p.grad.numpy()) == str(z["sha1/grad/" + n]), n
+        # the users' and brands' rows of E0 are the tables themselves: no GEMM on their path
+        _assert_matches_fixture(p.grad.numpy(), z, "grad/" + n,
+                                fusion and n.startswith("item_"))
 
 
 @pytest.mark.parametrize("name", CASES)
