@@ -3,6 +3,7 @@
     engine   ctypes binding of liblgcn_engine.so (include/lgcn.h), CSR plan cache, autograd
     graph    host-side normalised-adjacency builder (main.py:282-336) + synthetic generators
     loss     bpr_loss_reg with the reference signature (main.py:366-402)
+    train    bpr_step: one fused BPR training step that keeps the batch indices (main.py:495-525)
     dist     multi-GPU propagation (row partition + per-layer RCCL all-gather; feature split)
 """
 __version__ = "0.1.0"

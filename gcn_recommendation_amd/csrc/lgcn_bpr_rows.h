@@ -1,0 +1,169 @@
+// lgcn_bpr_rows.h — the BPR batch kernels shared by lgcn_bpr.hip (rows given as gathered
+// [B x d] blocks) and lgcn_bpr_step.hip (rows read from the tables by index): one row kernel,
+// templated on how sample b's six row pointers are obtained, and the fixed-order batch reduction.
+//
+//   loss = -mean_b log(sigmoid(<u_b,p_b> - <u_b,n_b>) + 1e-8)
+//          + lambda * (|U0|^2 + |P0|^2 + |N0|^2) / B
+//
+// Gradients follow autograd's chain for that expression: c_b = ((-1/B) / (s_b + 1e-8)) *
+// (1 - s_b) * s_b (NegBackward, MeanBackward, LogBackward, SigmoidBackward), du = c*p + (-c)*n,
+// dp = c*u, dn = (-c)*u, d(row0) = (2*lambda/B) * row0.
+#ifndef LGCN_BPR_ROWS_H_
+#define LGCN_BPR_ROWS_H_
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+namespace lgcn_bpr {
+
+constexpr int kWave = 64;
+constexpr int kRowsPerBlock = 4;  // one wave per batch row
+
+// the six rows of one sample: u, p, n (final) and u0, p0, n0 (layer 0)
+struct SampleRows {
+    const float* r[6];
+};
+
+// rows of six gathered blocks: sample b is row b of each
+struct GatheredRows {
+    const float* p[6];
+    int64_t ld[6];
+    __device__ __forceinline__ bool get(int64_t b, SampleRows& o) const {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) o.r[i] = p[i] + b * ld[i];
+        return true;
+    }
+};
+
+// rows of the tables themselves: sample b is (users[b], pos[b], neg[b]); tab = final user, final
+// item, layer-0 user, layer-0 item. A sample with an index outside its table has no rows (false)
+// and nothing of it is dereferenced.
+struct IndexedRows {
+    const float* tab[4];
+    int64_t ld[4];
+    const int64_t* users;
+    const int64_t* pos;
+    const int64_t* neg;
+    int64_t n_users, n_items;
+    __device__ __forceinline__ bool get(int64_t b, SampleRows& o) const {
+        const int64_t iu = users[b], ip = pos[b], in = neg[b];
+        if (iu < 0 || iu >= n_users || ip < 0 || ip >= n_items || in < 0 || in >= n_items)
+            return false;
+        o.r[0] = tab[0] + iu * ld[0];
+        o.r[1] = tab[1] + ip * ld[1];
+        o.r[2] = tab[1] + in * ld[1];
+        o.r[3] = tab[2] + iu * ld[2];
+        o.r[4] = tab[3] + ip * ld[3];
+        o.r[5] = tab[3] + in * ld[3];
+        return true;
+    }
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
+// grads = [6 x B x d] (u, p, n, u0, p0, n0); terms = [2 x B] (log term, squared norms). A sample
+// without rows (Rows::get false) contributes zero terms and zero gradient rows.
+template <typename Rows>
+__global__ __launch_bounds__(kWave * kRowsPerBlock) void k_bpr_rows(
+    Rows rows, int32_t B, int32_t d, float lambda, float* __restrict__ terms,
+    float* __restrict__ grads) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t b = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x / kWave;
+    if (b >= B) return;
+    const int64_t bd = (int64_t)B * d;
+    float* gu = grads;
+    float* gp = grads + bd;
+    float* gn = grads + 2 * bd;
+    float* gu0 = grads + 3 * bd;
+    float* gp0 = grads + 4 * bd;
+    float* gn0 = grads + 5 * bd;
+    SampleRows sr;
+    if (!rows.get(b, sr)) {
+        for (int k = lane; k < d; k += kWave) {
+            const int64_t o = b * (int64_t)d + k;
+            gu[o] = gp[o] = gn[o] = gu0[o] = gp0[o] = gn0[o] = 0.f;
+        }
+        if (lane == 0) terms[b] = terms[B + b] = 0.f;
+        return;
+    }
+    const float* ub = sr.r[0];
+    const float* pb = sr.r[1];
+    const float* nb = sr.r[2];
+    const float* ub0 = sr.r[3];
+    const float* pb0 = sr.r[4];
+    const float* nb0 = sr.r[5];
+    float sp = 0.f, sn = 0.f, sq = 0.f;
+    for (int k = lane; k < d; k += kWave) {
+        const float x = ub[k];
+        sp = __builtin_fmaf(x, pb[k], sp);
+        sn = __builtin_fmaf(x, nb[k], sn);
+        sq = __builtin_fmaf(ub0[k], ub0[k], sq);
+        sq = __builtin_fmaf(pb0[k], pb0[k], sq);
+        sq = __builtin_fmaf(nb0[k], nb0[k], sq);
+    }
+    sp = wave_sum(sp);
+    sn = wave_sum(sn);
+    sq = wave_sum(sq);
+    const float x = sp - sn;
+    const float s = 1.f / (1.f + expf(-x));
+    const float c = ((-1.f / (float)B) / (s + 1e-8f)) * (1.f - s) * s;
+    const float r = 2.f * lambda / (float)B;
+    for (int k = lane; k < d; k += kWave) {
+        const int64_t o = b * (int64_t)d + k;
+        gu[o] = c * pb[k] + (-c) * nb[k];
+        gp[o] = c * ub[k];
+        gn[o] = (-c) * ub[k];
+        gu0[o] = r * ub0[k];
+        gp0[o] = r * pb0[k];
+        gn0[o] = r * nb0[k];
+    }
+    if (lane == 0) {
+        terms[b] = logf(s + 1e-8f);
+        terms[B + b] = sq;
+    }
+}
+
+// loss = -(sum log terms) / B + lambda * (sum squares) / B, summed in a fixed order
+static __global__ __launch_bounds__(256) void k_bpr_reduce(const float* __restrict__ terms,
+                                                           int32_t B, float lambda,
+                                                           float* __restrict__ loss) {
+    __shared__ float sl[256], sr[256];
+    float a = 0.f, q = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        a += terms[i];
+        q += terms[B + i];
+    }
+    sl[threadIdx.x] = a;
+    sr[threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            sl[threadIdx.x] += sl[threadIdx.x + w];
+            sr[threadIdx.x] += sr[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = -(sl[0] / (float)B) + lambda * sr[0] / (float)B;
+}
+
+// both launches of one batch: rows kernel, then the reduction
+template <typename Rows>
+inline int launch(const Rows& rows, int32_t B, int32_t d, float lambda, float* terms, float* loss,
+                  float* grads, hipStream_t s) {
+    const int64_t grid = ((int64_t)B + kRowsPerBlock - 1) / kRowsPerBlock;
+    hipLaunchKernelGGL(k_bpr_rows<Rows>, dim3((uint32_t)grid), dim3(kWave * kRowsPerBlock), 0, s,
+                       rows, B, d, lambda, terms, grads);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_bpr_reduce, dim3(1), dim3(256), 0, s, terms, B, lambda, loss);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // namespace lgcn_bpr
+#endif  // LGCN_BPR_ROWS_H_

@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_PKG, "liblgcn_engine.so")
 
 # ---- ABI mirrors (include/lgcn.h) -------------------------------------------------------------
 LGCN_EPI_STORE, LGCN_EPI_MEAN, LGCN_EPI_ADD = 0, 1, 2
+LGCN_SCATTER_STORE, LGCN_SCATTER_ADD = 0, 1  # lgcn_rows_scatter modes
 LGCN_MAX_LAYERS = 16
 COO_ROWS_UNSORTED, COO_OUT_OF_RANGE, COO_COLS_UNSORTED = 1, 2, 4
 INT32_MAX = 2 ** 31 - 1
@@ -180,6 +181,13 @@ ABI = [
     ("lgcn_adj_finish", ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     ("lgcn_bpr_loss", ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
                                      _I32, _I32, ctypes.c_float, _P, _P, _P, _P]),
+    ("lgcn_bpr_loss_indexed", ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64,
+                                             _P, _P, _P, _I32, _I32, ctypes.c_float, _P, _P, _P,
+                                             _P]),
+    ("lgcn_bpr_keys", ctypes.c_int, [_P, _P, _P, _I32, _I64, _I64, _P, _P]),
+    ("lgcn_rows_scatter", ctypes.c_int, [_P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64, _I32, _I32,
+                                         _P, _P, _P]),
+    ("lgcn_rows_clear", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),
     ("lgcn_fusion_prelayer", ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
     ("lgcn_chain_max_default", ctypes.c_int32, [_I64]),
@@ -1465,7 +1473,7 @@ def _backward_role(dev, n, cnt, scale=1):
 
 
 def propagate_backward(graph, grad_out, K, hub_threshold=None, sparse=None, hub_mode=None,
-                       emu_min=None):
+                       emu_min=None, nz=None):
     """dE0 = Σ_k (Âᵀ)^k G/(K+1), Horner order h = G/(K+1) + Âᵀ h (autograd's accumulation).
 
     grad_out: the [n x d] upstream gradient, or a list of row blocks (the user / item / brand
@@ -1473,7 +1481,10 @@ def propagate_backward(graph, grad_out, K, hub_threshold=None, sparse=None, hub_
     load and every epilogue adds G[row]/(K+1) — the same rounding as a stored c.
     sparse: "auto" | "off" | "on" (default: env LGCN_SPARSE_GRAD): auto/on build G's row mask on
     the device, layer 1 gathers only G's live rows and the epilogues skip its zero rows — same
-    bits, fewer bytes for a BPR batch's G; off runs the dense kernels. Nothing is read back."""
+    bits, fewer bytes for a BPR batch's G; off runs the dense kernels. Nothing is read back.
+    nz: None, or (mask, count) of G's live rows as lgcn_rows_nonzero would compute them, from a
+    caller that already knows them (train.BprStepFunction's scatter): the mask pass, the dense
+    hint and the sampled count are skipped, the count still picks the sided schedule."""
     if hub_threshold is None:
         hub_threshold = hub_threshold_from_env()
     gt = graph.transpose
@@ -1492,9 +1503,9 @@ def propagate_backward(graph, grad_out, K, hub_threshold=None, sparse=None, hub_
             _check(lib.lgcn_scale_rows(g, n, d, 1.0, _ptr(out), d, stream), "lgcn_scale_rows")
             return out
         mode = sparse or _sparse_grad_mode()
-        nz = cnt = None
+        nz, cnt = nz if nz is not None else (None, None)
         scale = 1
-        if mode in ("auto", "on") and n > 0:
+        if nz is None and mode in ("auto", "on") and n > 0:
             # no host read-back (it would sync every step): the mask costs one pass over G (0.7 ms
             # at C3). When the previous calls' counts say G is dense, the mask would mark every
             # row: skip it (and the live-edge path it gates) and only sample G's rows for the

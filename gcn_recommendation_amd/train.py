@@ -1,0 +1,241 @@
+"""One call for a BPR training step (main.py:495-525) that keeps the batch indices.
+
+main.py's route — `model(adj)`, six advanced-index gathers, `bpr_loss_reg`, `loss.backward()` —
+makes autograd zero-fill and index_put six dense [rows x d] gradients, after which the engine's
+backward searches the dense G for its few thousand live rows again (lgcn_rows_nonzero) and reads
+the two dense ego gradients in full (lgcn_add_nonzero). `bpr_step` runs the same arithmetic with
+the indices in hand:
+
+    forward   propagate_forward, then lgcn_bpr_loss_indexed on views of its output buffer and of
+              the layer-0 tables (no gathered copies); the six per-sample gradient blocks are kept
+    backward  the 3B destination keys sorted once (lgcn_bpr_keys, lgcn_coo_sort_perm); the three
+              final-row blocks STORE-scattered into a zero workspace together with G's row mask
+              and live-row count (lgcn_rows_scatter); propagate_backward on the workspace with
+              that mask; the three layer-0 blocks ADD-scattered into dE0's touched rows; the
+              workspace rows cleared again (lgcn_rows_clear)
+
+Loss and every parameter gradient are bitwise those of main.py's route: the scatter sums each
+destination row in autograd's order (per row from +0 in ascending batch position, an item row's
+positive run plus its negative run). Nothing is read back to the host and everything is issued on
+the caller's current stream. The brand-loss branch of bpr_loss_reg is not part of this entry point.
+"""
+import ctypes
+import weakref
+
+import torch
+
+from . import engine
+from .loss import bpr_loss_reg
+
+
+class _Workspace:
+    """Per (graph, d): the dense [n x d] zero block the final-row gradients are scattered into
+    (the autograd route allocates and zero-fills as much every step), its row mask and live-row
+    count, and sort scratch for the largest batch seen. Invariant: G, mask and count are all zero
+    on entry to and on exit from a step; a step that raises in between leaves `dirty` set and the
+    next one re-zeroes them whole. One backward at a time per graph: steps issued on different
+    streams at once would share it."""
+
+    def __init__(self, n, d, device):
+        self.n, self.d, self.device = n, d, device
+        self.G = torch.zeros((n, d), dtype=torch.float32, device=device)
+        self.mask = torch.zeros(max((n + 31) // 32, 1), dtype=torch.int32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        self.dirty = False
+        self.cap = 0
+        self.temp = self.temp_for = None
+
+    def sort_scratch(self, lib, m, n_keys, stream):
+        """Buffers of lgcn_coo_sort_perm for m keys (grown, never shrunk)."""
+        if m > self.cap:
+            dev = self.device
+            self.keys = torch.empty(m, dtype=torch.int64, device=dev)
+            self.i32 = torch.empty((4, m), dtype=torch.int32, device=dev)
+            self.cap = m
+        if self.temp_for != (m, n_keys):
+            nbytes = ctypes.c_size_t(0)
+            b = self.i32
+            engine._check(lib.lgcn_coo_sort_perm(None, m, n_keys, engine._ptr(b[0]),
+                                                 engine._ptr(b[1]), engine._ptr(b[2]),
+                                                 engine._ptr(b[3]), None, ctypes.byref(nbytes),
+                                                 stream), "lgcn_coo_sort_perm(size)")
+            if self.temp is None or self.temp.numel() < nbytes.value:
+                self.temp = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=self.device)
+            self.temp_bytes, self.temp_for = nbytes.value, (m, n_keys)
+
+    def rezero(self):
+        self.G.zero_()
+        self.mask.zero_()
+        self.count.zero_()
+        self.dirty = False
+
+
+_graphs = weakref.WeakSet()  # graphs that own workspaces (graph._bpr_workspaces: d -> _Workspace)
+
+
+def _workspace(graph, d):
+    table = graph.__dict__.setdefault("_bpr_workspaces", {})
+    ws = table.get(d)
+    if ws is None:
+        ws = table[d] = _Workspace(graph.n_rows, d, graph.device)
+        _graphs.add(graph)
+    return ws
+
+
+def release_workspace(graph=None):
+    """Free the step workspaces of `graph` (an engine.Graph), or of every graph."""
+    for g in [graph] if graph is not None else list(_graphs):
+        g.__dict__.pop("_bpr_workspaces", None)
+        _graphs.discard(g)
+
+
+def _scatter(lib, ws, m, src, lo, hi, dst, mode, mask, count, stream):
+    engine._check(lib.lgcn_rows_scatter(engine._ptr(ws.i32[1]), engine._ptr(ws.i32[3]), m,
+                                        engine._ptr(src), src.stride(0), lo, hi, engine._ptr(dst),
+                                        dst.stride(0), ws.d, mode, engine._ptr(mask),
+                                        engine._ptr(count), stream), "lgcn_rows_scatter")
+
+
+class BprStepFunction(torch.autograd.Function):
+    """(graph, K, hub_threshold, lambda_reg, users, pos, neg, n_e0, *segments) -> the loss.
+
+    Mirrors engine.PropagateFunction: segments = the (user, item, brand) layer-0 blocks the
+    propagation reads; the first n_e0 of them are also the tables the regulariser's rows come
+    from. n_e0 = 2 (LightGCN): user and item. n_e0 = 1 (LightGCN_Fusion): the user block only —
+    the item block is the pre-layer's output, and one more tensor follows the segments, the item
+    id table the regulariser reads, whose gradient (row-sparse, a fresh zero tensor filled by the
+    scatter) is returned for it."""
+
+    @staticmethod
+    def forward(ctx, graph, K, hub_threshold, lambda_reg, users, pos, neg, n_e0, *segments):
+        if n_e0 not in (1, 2):
+            raise engine.LgcnError(f"bpr_step: n_e0={n_e0} (1 or 2)")
+        nseg = len(segments) - (2 - n_e0)
+        if nseg < 2:
+            raise engine.LgcnError("bpr_step: user and item segments expected")
+        lib = engine.load_library()
+        dev = graph.device
+        segs = [t.detach() for t in segments[:nseg]]
+        sizes = [int(t.shape[0]) for t in segs]
+        U, I = sizes[0], sizes[1]
+        out = engine.propagate_forward(graph, segs, K, hub_threshold)
+        d = int(out.shape[1])
+        i0 = segs[1] if n_e0 == 2 else segments[nseg].detach()
+        if i0.shape != (I, d) or i0.dtype != torch.float32 or i0.device != dev or \
+                (I > 0 and i0.stride(1) != 1):
+            raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
+        B = int(users.shape[0])
+        fu, fi, u0 = out[:U], out[U:U + I], segs[0]
+        terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((6, B, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_bpr_loss_indexed(
+                engine._ptr(fu), d, engine._ptr(fi), d, engine._ptr(u0), d, engine._ptr(i0),
+                i0.stride(0) if I else d, U, I, engine._ptr(users), engine._ptr(pos),
+                engine._ptr(neg), B, d, float(lambda_reg), engine._ptr(terms), engine._ptr(loss),
+                engine._ptr(grads), engine._stream(dev)), "lgcn_bpr_loss_indexed")
+        ctx.save_for_backward(grads, users, pos, neg)
+        ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
+        ctx.sizes, ctx.n_e0, ctx.n_inputs = sizes, n_e0, len(segments)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads, users, pos, neg = ctx.saved_tensors
+        graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
+        U, I = sizes[0], sizes[1]
+        _, B, d = grads.shape
+        m = 3 * B
+        lib = engine.load_library()
+        dev = graph.device
+        sg = (grads * g).view(2, m, d)  # BPRLossFunction.backward's scaling, all six blocks
+        ws = _workspace(graph, d)
+        gi = None
+        with torch.cuda.device(dev):
+            stream = engine._stream(dev)
+            if ws.dirty:
+                ws.rezero()
+            n_keys = 2 * (U + I) + 1
+            ws.sort_scratch(lib, m, n_keys, stream)
+            engine._check(lib.lgcn_bpr_keys(engine._ptr(users), engine._ptr(pos), engine._ptr(neg),
+                                            B, U, I, engine._ptr(ws.keys), stream), "lgcn_bpr_keys")
+            b = ws.i32
+            nbytes = ctypes.c_size_t(ws.temp_bytes)
+            engine._check(lib.lgcn_coo_sort_perm(engine._ptr(ws.keys), m, n_keys, engine._ptr(b[0]),
+                                                 engine._ptr(b[1]), engine._ptr(b[2]),
+                                                 engine._ptr(b[3]), engine._ptr(ws.temp),
+                                                 ctypes.byref(nbytes), stream),
+                          "lgcn_coo_sort_perm")
+            ws.dirty = True
+            _scatter(lib, ws, m, sg[0], 0, U + I, ws.G, engine.LGCN_SCATTER_STORE, ws.mask,
+                     ws.count, stream)
+            g0 = engine.propagate_backward(graph, ws.G, ctx.K, ctx.hub_threshold,
+                                           nz=(ws.mask, ws.count))
+            _scatter(lib, ws, m, sg[1], 0, U + I if n_e0 == 2 else U, g0,
+                     engine.LGCN_SCATTER_ADD, None, None, stream)
+            if n_e0 == 1:
+                gi = torch.zeros((I, d), dtype=torch.float32, device=dev)
+                _scatter(lib, ws, m, sg[1], U, U + I, gi, engine.LGCN_SCATTER_STORE, None, None,
+                         stream)
+            engine._check(lib.lgcn_rows_clear(engine._ptr(b[1]), m, 0, U + I, engine._ptr(ws.G), d,
+                                              d, engine._ptr(ws.mask), engine._ptr(ws.count),
+                                              stream), "lgcn_rows_clear")
+            ws.dirty = False
+        blocks = tuple(torch.split(g0, sizes, 0))
+        return (None,) * 8 + blocks + ((gi,) if n_e0 == 1 else ())
+
+
+def _check_index_tensors(users, pos, neg, device):
+    B = None
+    for name, t in (("users", users), ("pos", pos), ("neg", neg)):
+        if not torch.is_tensor(t) or t.dtype != torch.int64:
+            raise engine.LgcnError(f"bpr_step: {name} must be an int64 tensor "
+                                   f"(got {getattr(t, 'dtype', type(t))})")
+        if t.dim() != 1:
+            raise engine.LgcnError(f"bpr_step: {name} must be 1-D, got {tuple(t.shape)}")
+        if t.device != device:
+            raise engine.LgcnError(f"bpr_step: {name} on {t.device}, adjacency on {device}")
+        if B is None:
+            B = int(t.shape[0])
+        elif int(t.shape[0]) != B:
+            raise engine.LgcnError("bpr_step: users, pos and neg must have one length")
+    if B < 1:
+        raise engine.LgcnError("bpr_step: empty batch")
+
+
+def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False):
+    """The loss of one BPR batch (main.py:495-522 with brand_loss off) as a tensor whose
+    `.backward()` leaves exactly the parameter `.grad`s main.py's route leaves:
+
+        optimizer.zero_grad()
+        loss = model.bpr_step(adj, users, pos, neg, weight_decay)
+        loss.backward(); optimizer.step()
+
+    users / pos / neg: 1-D int64 tensors on the adjacency's device (wrong dtype, device or rank
+    raises LgcnError before any launch). check_indices=True also validates them against the table
+    sizes with torch ops first (one sync) and raises LgcnError; by default nothing is checked or
+    synchronised — the kernels are memory-safe either way (a sample with an index outside its
+    table is skipped). On a CPU adjacency the reference's own expression runs (model(adj), the
+    gathers, the torch formula): the device dispatch of the models and loss.py. The brand-loss
+    branch of bpr_loss_reg is not part of this entry point."""
+    _check_index_tensors(users, pos, neg, adj.device)
+    U, I = model.num_users, model.num_items
+    if check_indices:
+        for name, t, n in (("users", users, U), ("pos", pos, I), ("neg", neg, I)):
+            if bool(((t < 0) | (t >= n)).any()):
+                raise engine.LgcnError(f"bpr_step: {name} holds an index outside [0, {n})")
+    if adj.device.type != "cuda":
+        fu, fi, fb, u0, i0 = model(adj)
+        return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg], lambda_reg,
+                            final_brand_emb=fb)
+    n_e0 = model._bpr_n_e0
+    if n_e0 == 2:
+        tensors = [model.user_embedding.weight, model.item_embedding.weight,
+                   model.brand_embedding.weight]
+    else:
+        tensors = [model.user_embedding.weight, model.fused_item_embedding(),
+                   model.brand_embedding.weight, model.item_id_embedding.weight]
+    graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
+    return BprStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                 float(lambda_reg), users, pos, neg, n_e0, *tensors)

@@ -43,6 +43,9 @@
 extern "C" {
 #endif
 
+/* 14 since the sided propagation; the training-step entry points (lgcn_bpr_loss_indexed,
+ * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) were added without a bump: purely additive,
+ * no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -619,6 +622,52 @@ int lgcn_bpr_loss(const float* u, int64_t ldu, const float* p, int64_t ldp, cons
                   int64_t ldn, const float* u0, int64_t ldu0, const float* p0, int64_t ldp0,
                   const float* n0, int64_t ldn0, int32_t B, int32_t d, float lambda, float* terms,
                   float* loss, float* grads, void* stream);
+
+/* ---- fused training step: the batch indices kept (main.py:495-525) --------------------------- */
+/* lgcn_bpr_loss with the six row blocks read straight from the tables: sample b uses rows
+ * users[b] of fu (final user table) and u0 (layer-0 user table), pos[b] / neg[b] of fi and i0
+ * (final and layer-0 item tables); users / pos / neg are device int64 [B]. Same kernels, so loss
+ * and grads ([6 x B x d], lgcn_bpr_loss's order) are bitwise those of lgcn_bpr_loss on gathered
+ * copies. A sample with an index outside [0, n_users) / [0, n_items) is skipped: nothing of it is
+ * dereferenced, its terms and gradient rows are zero. terms: scratch [2 x B]. */
+int lgcn_bpr_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                          const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                          int64_t n_users, int64_t n_items, const int64_t* users,
+                          const int64_t* pos, const int64_t* neg, int32_t B, int32_t d,
+                          float lambda, float* terms, float* loss, float* grads, void* stream);
+
+/* Destination keys of the batch's 3B per-sample gradient rows (rows [0,B) users, [B,2B) positive,
+ * [2B,3B) negative items), keys [3 x B] int64 for lgcn_coo_sort_perm: 2 * row + is_neg, row in
+ * the numbering of lgcn_propagate_backward's grad_out (user u -> u, item i -> n_users + i). All
+ * three keys of a skipped sample (see above) are 2 * (n_users + n_items), past every row: sort
+ * with n_keys = 2 * (n_users + n_items) + 1. */
+int lgcn_bpr_keys(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B,
+                  int64_t n_users, int64_t n_items, int64_t* keys, void* stream);
+
+/* Deterministic scatter-accumulate of n contributions into table rows. Contribution j (in sorted
+ * order) has key keys_sorted[j] = 2 * row + sub and source row perm[j] of src [n x ld_src] —
+ * keys_sorted / perm from lgcn_coo_sort_perm (stable: equal keys keep their batch order). Only
+ * rows in [row_lo, row_hi) are written; row r lands in dst row r - row_lo (bit r - row_lo of
+ * mask). Per destination row and column: (+0 + the sub = 0 contributions in sorted order) +
+ * (+0 + the sub = 1 ones) — what IndexBackward's sequential index_put into zeros and autograd's
+ * sum of the positive and negative item blocks give; plain fp32 adds, one wave per row, no float
+ * atomics.
+ *  STORE: dst row = that sum (dst all zero on entry: untouched rows stay zero); mask (NULL = none;
+ *    zero on entry) gets the row's bit iff the sum holds a value != 0 (NaN included) and *count
+ *    (NULL = none; zero on entry) the number of such rows — lgcn_rows_nonzero's of the dense dst.
+ *  ADD: dst row = dst row + that sum, one add per element, touched rows only (an untouched row
+ *    would receive +0: no change unless it held -0). mask and count must be NULL. */
+#define LGCN_SCATTER_STORE 0
+#define LGCN_SCATTER_ADD   1
+int lgcn_rows_scatter(const int32_t* keys_sorted, const int32_t* perm, int32_t n, const float* src,
+                      int64_t ld_src, int32_t row_lo, int32_t row_hi, float* dst, int64_t ld_dst,
+                      int32_t d, int32_t mode, uint32_t* mask, int32_t* count, void* stream);
+
+/* Undo a STORE scatter without touching the whole block: zero the dst rows the keys name (those
+ * in [row_lo, row_hi)), the mask words they fall in (mask NULL = none) and *count (NULL = none). */
+int lgcn_rows_clear(const int32_t* keys_sorted, int32_t n, int32_t row_lo, int32_t row_hi,
+                    float* dst, int64_t ld_dst, int32_t d, uint32_t* mask, int32_t* count,
+                    void* stream);
 
 /* ---- LightGCN_Fusion item pre-layer (models/lightgcn_fusion.py:45-49) ------------------------ */
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,

@@ -11,7 +11,7 @@ CPU-only host — never a fallback for a HIP tensor: the engine raises if it can
 import torch
 import torch.nn as nn
 
-from gcn_recommendation_amd import engine
+from gcn_recommendation_amd import engine, train
 
 
 class LightGCN(nn.Module):
@@ -108,6 +108,15 @@ class LightGCN(nn.Module):
         cos_sim = torch.nn.functional.cosine_similarity(
             item_emb_with_brand, item_emb_no_brand, dim=1).mean()
         print(f"Average cos similarity (item emb with/without brand): {cos_sim.item():.6f}")
+
+    # -- fused training step (gcn_recommendation_amd.train) --------------------------------------
+    _bpr_n_e0 = 2  # the regulariser's user and item rows come from the propagation's segments
+
+    def bpr_step(self, adj, users, pos, neg, lambda_reg):
+        """The BPR + L2 loss of one batch (main.py:495-522 without the brand loss) in one call
+        that keeps the batch indices: `.backward()` leaves the `.grad`s of the hand-written
+        route, to the bit (train.bpr_step)."""
+        return train.bpr_step(self, adj, users, pos, neg, lambda_reg)
 
     # -- LightGCN-style accessor (north_star "computer()") --------------------------------------
     def set_graph(self, adj_mat):

@@ -11,7 +11,7 @@ E0 = [user | fused_item | brand] as three segments.
 import torch
 import torch.nn as nn
 
-from gcn_recommendation_amd import engine, fusion
+from gcn_recommendation_amd import engine, fusion, train
 
 
 class LightGCN_Fusion(nn.Module):
@@ -62,6 +62,14 @@ class LightGCN_Fusion(nn.Module):
             final_user_emb, final_item_emb, final_brand_emb = torch.split(
                 final_embeddings, [self.num_users, self.num_items, self.num_brands])
         return final_user_emb, final_item_emb, final_brand_emb, user_emb_0, item_id_emb_0
+
+    _bpr_n_e0 = 1  # only the user rows: the item segment is the pre-layer's output
+
+    def bpr_step(self, adj, users, pos, neg, lambda_reg):
+        """The BPR + L2 loss of one batch in one call that keeps the batch indices
+        (train.bpr_step): the item segment is the pre-layer's output and keeps its autograd
+        graph, the item regulariser rows come from item_id_embedding.weight."""
+        return train.bpr_step(self, adj, users, pos, neg, lambda_reg)
 
     def set_graph(self, adj_mat):
         self._graph_adj = adj_mat
