@@ -3,13 +3,25 @@
     engine   ctypes binding of liblgcn_engine.so (include/lgcn.h), CSR plan cache, autograd
     graph    host-side normalised-adjacency builder (main.py:282-336) + synthetic generators
     loss     bpr_loss_reg with the reference signature (main.py:366-402)
-    train    bpr_step: one fused BPR training step that keeps the batch indices (main.py:495-525)
+    train    bpr_step: one fused BPR training step that keeps the batch indices (main.py:495-525);
+             bpr_epoch: a whole epoch of them fed by the sampler
+    sampler  BprSampler: the negatives of a whole epoch in one launch (main.py:349-363)
     dist     multi-GPU propagation (row partition + per-layer RCCL all-gather; feature split)
 """
 __version__ = "0.1.0"
 
+import importlib as _importlib
 import os as _os
 import sys as _sys
+
+
+
+def __getattr__(name):
+    # `gcn_recommendation_amd.sampler` on first use: importing the package itself still imports
+    # neither torch nor the engine
+    if name == "sampler":
+        return _importlib.import_module(f"{__name__}.sampler")
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _raise_hw_queues():

@@ -26,6 +26,7 @@ COO_ROWS_UNSORTED, COO_OUT_OF_RANGE, COO_COLS_UNSORTED = 1, 2, 4
 INT32_MAX = 2 ** 31 - 1
 TUNE_ROWS_PER_GROUP, TUNE_UNROLL, TUNE_MEAN_PREFETCH, TUNE_MIN_GROUPS = 1, 2, 3, 4
 TUNE_EMU_MARGIN = 6
+TUNE_SAMPLE_BLOCKS = 7
 SCHED_SLOTS0, SCHED_SLOTS1, SCHED_CHAIN, SCHED_TIMING_START, SCHED_TIMING_END, SCHED_TRACE = \
     1, 2, 3, 4, 5, 6
 SCHED_TRACE_SIDES, SCHED_TIMING_SIDES = 7, 8
@@ -188,6 +189,8 @@ ABI = [
     ("lgcn_rows_scatter", ctypes.c_int, [_P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64, _I32, _I32,
                                          _P, _P, _P]),
     ("lgcn_rows_clear", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),
+    ("lgcn_bpr_sample", ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64,
+                                       ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P, _P, _P]),
     ("lgcn_fusion_prelayer", ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
     ("lgcn_chain_max_default", ctypes.c_int32, [_I64]),

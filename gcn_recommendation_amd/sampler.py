@@ -1,0 +1,288 @@
+"""The BPR negative sampler (main.py:349-363, BPRDataset behind a DataLoader) without the Python
+call per interaction: one draw for a whole epoch, on the device the training step runs on.
+
+    sampler = BprSampler(train_df['user_idx'], train_df['item_idx'], U, I, device, seed=0)
+    for users, pos, neg in sampler.epoch(epoch, batch_size):      # views of one draw
+        loss = model.bpr_step(adj, users, pos, neg, weight_decay)
+
+The draw (include/lgcn.h, lgcn_bpr_sample; DESIGN §5 "Sampler"). The negative of interaction idx
+— its index in the arrays the sampler was built from — is a pure function of (seed, epoch, idx, the
+user's positive list, num_items):
+
+    r64   = Philox4x32-10(counter (idx_lo32, idx_hi32, epoch, 0), key (seed_lo32, seed_hi32)),
+            r64 = out[1] << 32 | out[0]
+    j     = mulhi64(r64, n_free),  n_free = num_items - deg(user)
+    neg   = j + m,  m = #{t : L[t] - t <= j},  L = the user's sorted, de-duplicated items
+
+i.e. the j-th item the user has not interacted with: uniform over the complement, the
+distribution of the reference's rejection loop, without the loop. A user with every item as a
+positive (the reference never returns for one) gets neg = -1 and is counted in `unsampled`;
+bpr_step skips such a sample on a HIP device. Batch size, shuffle order, first / count windows and
+the launch geometry do not enter the draw; `epoch` and `seed` do.
+
+Device dispatch, as the models and loss.py: a HIP `device` runs csrc/lgcn_sampler.hip (no
+fallback), a CPU `device` runs the same arithmetic as vectorised numpy — what a CPU-only user
+gets, and the reference the GPU tests compare the kernel against, bit for bit.
+"""
+import ctypes
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import engine
+from .evaluate import mask_csr
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+SHUFFLE_MIX = 0x9E3779B97F4A7C15  # epoch()'s permutation seed: (seed + SHUFFLE_MIX * epoch) mod 2^63
+INT31 = 1 << 31
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on arrays (or scalars) of 32-bit words: counter (c0..c3), key (k0, k1) ->
+    the four output words as uint32 arrays."""
+    c = [np.asarray(x, dtype=np.uint64) & _MASK32 for x in (c0, c1, c2, c3)]
+    c = list(np.broadcast_arrays(*c))
+    k0 = np.asarray(k0, dtype=np.uint64) & _MASK32
+    k1 = np.asarray(k1, dtype=np.uint64) & _MASK32
+    m0, m1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]   # 32 x 32 -> 64 bits: exact in uint64
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _MASK32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _MASK32]
+        k0 = (k0 + np.uint64(PHILOX_W0)) & _MASK32
+        k1 = (k1 + np.uint64(PHILOX_W1)) & _MASK32
+    return tuple(x.astype(np.uint32) for x in c)
+
+
+def mulhi64(r64, n):
+    """The high 64 bits of r64 * n for uint64 r64 and 0 <= n < 2^31, exactly, without 128-bit
+    integers: (hi * n + ((lo * n) >> 32)) >> 32 — both products and the sum stay below 2^64."""
+    r64 = np.asarray(r64, dtype=np.uint64)
+    n = np.asarray(n, dtype=np.uint64)
+    hi, lo = r64 >> _S32, r64 & _MASK32
+    return (hi * n + ((lo * n) >> _S32)) >> _S32
+
+
+def random_j(idx, n_free, seed, epoch):
+    """j = mulhi64(r64(seed, epoch, idx), n_free) per element (int64)."""
+    idx = np.asarray(idx, dtype=np.int64).astype(np.uint64)
+    seed = int(seed)
+    o0, o1, _, _ = philox4x32_10(idx & _MASK32, idx >> _S32, np.uint64(int(epoch)), np.uint64(0),
+                                 np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF))
+    r64 = (o1.astype(np.uint64) << _S32) | o0.astype(np.uint64)
+    return mulhi64(r64, n_free).astype(np.int64)
+
+
+def kth_missing(pos_rowptr, pos_items, users, j):
+    """Per element the j-th (0-based) item missing from its user's sorted list L: j + m with
+    m = #{t : L[t] - t <= j}, by the kernel's upper-bound binary search (L[t] - t is
+    non-decreasing), every element's search advanced one step per vectorised round; elements
+    drop out as their interval closes, so the rounds after the first few touch only the users
+    with long lists."""
+    rowptr = np.asarray(pos_rowptr)
+    items = np.asarray(pos_items)
+    users = np.asarray(users, dtype=np.int64)
+    j = np.asarray(j, dtype=np.int64)
+    base = rowptr[users].astype(np.int64)
+    lo, hi = base.copy(), rowptr[users + 1].astype(np.int64)
+    act = np.nonzero(lo < hi)[0]
+    while act.size:
+        l, h = lo[act], hi[act]
+        mid = (l + h) >> 1
+        up = items[mid] - (mid - base[act]) <= j[act]
+        l, h = np.where(up, mid + 1, l), np.where(up, h, mid)
+        lo[act], hi[act] = l, h
+        act = act[l < h]
+    return j + (lo - base)
+
+
+CHUNK = 1 << 16  # slots per piece of the numpy path: its temporaries stay in cache
+
+
+def sample_numpy(inter_user, inter_item, order, first, count, pos_rowptr, pos_items, n_users,
+                 n_items, seed, epoch):
+    """lgcn_bpr_sample's contract on the host, vectorised: (users, pos, neg) int64 arrays of
+    `count` slots and the number of samples left without a negative. Slots whose interaction
+    index or user lies outside its range are -1 in all three, as the kernel writes them. Runs in
+    pieces of CHUNK slots on a few threads (numpy releases the GIL; a slot's result does not
+    depend on the split)."""
+    inter_user = np.asarray(inter_user)
+    inter_item = np.asarray(inter_item)
+    rowptr = np.asarray(pos_rowptr)
+    items = np.asarray(pos_items)
+    order = None if order is None else np.asarray(order, dtype=np.int64)
+    users = np.full(count, -1, dtype=np.int64)
+    pos = np.full(count, -1, dtype=np.int64)
+    neg = np.full(count, -1, dtype=np.int64)
+
+    def piece(b):
+        e = min(b + CHUNK, count)
+        idx = np.arange(first + b, first + e, dtype=np.int64)
+        if order is not None:
+            idx = order[idx]
+        sel = np.nonzero((idx >= 0) & (idx < inter_user.shape[0]))[0]
+        u = inter_user[idx[sel]].astype(np.int64)
+        ok = (u >= 0) & (u < n_users)
+        sel, u = sel[ok], u[ok]
+        idx = idx[sel]
+        users[b:e][sel] = u
+        pos[b:e][sel] = inter_item[idx]
+        n_free = n_items - (rowptr[u + 1].astype(np.int64) - rowptr[u])
+        free = n_free > 0
+        j = random_j(idx[free], n_free[free], seed, epoch)
+        neg[b:e][sel[free]] = kth_missing(rowptr, items, u[free], j)
+        return int(free.size - free.sum())
+
+    starts = range(0, count, CHUNK)
+    if len(starts) > 1:
+        with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
+            missed = sum(pool.map(piece, starts))
+    else:
+        missed = sum(piece(b) for b in starts)
+    return users, pos, neg, missed
+
+
+def sample_device(inter_user, inter_item, order, first, count, pos_rowptr, pos_items, n_users,
+                  n_items, seed, epoch, unsampled=None):
+    """lgcn_bpr_sample on the HIP device of `inter_user` (int32 tensors; order: int64 or None),
+    on the caller's current stream: (users, pos, neg) int64 tensors of `count` slots. unsampled:
+    None, or the device int32 counter the kernel adds to (the caller zeroes it)."""
+    lib = engine.load_library()
+    dev = inter_user.device
+    for name, t, dt in (("inter_user", inter_user, torch.int32), ("inter_item", inter_item,
+                                                                   torch.int32),
+                        ("pos_rowptr", pos_rowptr, torch.int32), ("pos_items", pos_items,
+                                                                  torch.int32),
+                        ("order", order, torch.int64), ("unsampled", unsampled, torch.int32)):
+        if t is None:
+            continue
+        if t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise engine.LgcnError(f"sampler: {name} must be a contiguous {dt} tensor on {dev}")
+    if order is not None and first + count > order.numel():
+        raise engine.LgcnError(f"sampler: first + count = {first + count} past the order's "
+                               f"{order.numel()} entries")
+    if pos_rowptr.numel() != n_users + 1:
+        raise engine.LgcnError("sampler: pos_rowptr must hold num_users + 1 entries")
+    if first < 0 or count < 0:
+        raise engine.LgcnError("sampler: negative first or count")
+    out = torch.empty((3, count), dtype=torch.int64, device=dev)
+    if count == 0:  # nothing to launch (and an empty tensor has no pointer to pass)
+        return out[0], out[1], out[2]
+    P = engine._ptr
+    with torch.cuda.device(dev):
+        engine._check(lib.lgcn_bpr_sample(
+            P(inter_user), P(inter_item), inter_user.numel(), P(order), first, count,
+            P(pos_rowptr), P(pos_items), n_users, n_items, ctypes.c_uint64(int(seed)),
+            ctypes.c_uint32(int(epoch)), P(out[0]), P(out[1]), P(out[2]), P(unsampled),
+            engine._stream(dev)), "lgcn_bpr_sample")
+    return out[0], out[1], out[2]
+
+
+class BprSampler:
+    """BprSampler(users, items, num_users, num_items, device, seed=0)
+
+    users / items: the train interactions (train_df['user_idx'], train_df['item_idx']), each one
+    a sample as in BPRDataset, duplicates included. Built once: the per-user positive lists are
+    evaluate.mask_csr's (sorted, de-duplicated; numpy, no groupby), uploaded with the interactions
+    as int32. len(sampler) = the number of interactions."""
+
+    def __init__(self, users, items, num_users, num_items, device, seed=0):
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int64))
+        items = np.ascontiguousarray(np.asarray(items, dtype=np.int64))
+        if users.ndim != 1 or users.shape != items.shape:
+            raise ValueError("BprSampler: users and items must be 1-D and of one length")
+        num_users, num_items = int(num_users), int(num_items)
+        if not (0 <= num_users < INT31 and 0 <= num_items < INT31 and users.size < INT31):
+            raise ValueError("BprSampler: num_users, num_items and the interaction count must be "
+                             "below 2^31")
+        if users.size and (users.min() < 0 or users.max() >= num_users or items.min() < 0
+                           or items.max() >= num_items):
+            raise ValueError("BprSampler: an interaction lies outside [0, num_users) x "
+                             "[0, num_items)")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("BprSampler: seed must fit 64 unsigned bits")
+        self.num_users, self.num_items, self.seed = num_users, num_items, seed
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            # main.py:59 builds torch.device('cuda'); tensors report 'cuda:<current>', and the two
+            # compare unequal: keep the indexed form every later comparison meets
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        rowptr, pos_items = mask_csr(users, items, num_users)
+        self._n = int(users.size)
+        host = (users.astype(np.int32), items.astype(np.int32), rowptr,
+                np.ascontiguousarray(pos_items, dtype=np.int32))
+        if self.device.type == "cuda":
+            engine.load_library()  # a missing kernel is an error, here and not at the first draw
+            self._user, self._item, self._rowptr, self._pos_items = (
+                torch.from_numpy(a).to(self.device) for a in host)
+            if self._pos_items.numel() == 0:
+                self._pos_items = torch.zeros(1, dtype=torch.int32, device=self.device)
+        else:
+            self._user, self._item, self._rowptr, self._pos_items = host
+        # samples of the latest draw left without a negative (users with no free item)
+        self.unsampled = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return self._n
+
+    def draw(self, epoch, order=None, first=0, count=None):
+        """(users, pos, neg): int64 tensors on the sampler's device for output slots [0, count):
+        slot s is interaction order[first + s] (order: an int64 index tensor on the device, e.g. a
+        permutation; None = identity). count=None: up to the end of the order. One launch on the
+        current stream, no host read-back; `unsampled` is reset and counts this draw."""
+        epoch = int(epoch)
+        if not 0 <= epoch < 1 << 32:
+            raise ValueError("BprSampler.draw: epoch must fit 32 unsigned bits")
+        total = self._n if order is None else int(order.numel())
+        first = int(first)
+        count = total - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > total:
+            raise ValueError(f"BprSampler.draw: window [{first}, {first + count}) outside the "
+                             f"{total} entries")
+        if self.device.type == "cuda":
+            if order is not None and (not torch.is_tensor(order) or order.dtype != torch.int64
+                                      or order.device != self.device or order.dim() != 1):
+                raise engine.LgcnError("BprSampler.draw: order must be a 1-D int64 tensor on "
+                                       f"{self.device}")
+            self.unsampled.zero_()
+            return sample_device(self._user, self._item,
+                                 None if order is None else order.contiguous(), first, count,
+                                 self._rowptr, self._pos_items, self.num_users, self.num_items,
+                                 self.seed, epoch, self.unsampled)
+        if torch.is_tensor(order):
+            order = order.numpy()
+        u, p, n, missed = sample_numpy(self._user, self._item, order, first, count, self._rowptr,
+                                       self._pos_items, self.num_users, self.num_items, self.seed,
+                                       epoch)
+        self.unsampled.fill_(missed)
+        return torch.from_numpy(u), torch.from_numpy(p), torch.from_numpy(n)
+
+    def permutation(self, epoch):
+        """epoch()'s shuffle: torch.randperm(len, generator=g, device=device) with g a generator
+        of the sampler's device seeded (seed + SHUFFLE_MIX * epoch) mod 2^63. The order is an
+        input of the draw, not part of its contract: the CPU and HIP generators give different
+        permutations of the same seed, the negative of an interaction is the same under both."""
+        g = torch.Generator(device=self.device)
+        g.manual_seed((self.seed + SHUFFLE_MIX * int(epoch)) % (1 << 63))
+        return torch.randperm(self._n, generator=g, device=self.device)
+
+    def epoch(self, epoch, batch_size, shuffle=True, drop_last=False):
+        """One draw for the whole epoch (one launch), made by this call (so `unsampled` counts it
+        on return), then an iterator of (users, pos, neg) views of it batch by batch: no launch,
+        copy or sync per batch. The last batch is short unless drop_last."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("BprSampler.epoch: batch_size must be positive")
+        users, pos, neg = self.draw(epoch, self.permutation(epoch) if shuffle else None)
+        end = self._n - self._n % batch_size if drop_last else self._n
+
+        def views():
+            for b in range(0, end, batch_size):
+                e = min(b + batch_size, end)
+                yield users[b:e], pos[b:e], neg[b:e]
+        return views()

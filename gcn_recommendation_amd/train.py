@@ -18,6 +18,9 @@ Loss and every parameter gradient are bitwise those of main.py's route: the scat
 destination row in autograd's order (per row from +0 in ascending batch position, an item row's
 positive run plus its negative run). Nothing is read back to the host and everything is issued on
 the caller's current stream. The brand-loss branch of bpr_loss_reg is not part of this entry point.
+
+`bpr_epoch` is the loop around it (main.py:488-531): the batches are views of one device-side draw
+of sampler.BprSampler, the per-batch losses come back as one device tensor.
 """
 import ctypes
 import weakref
@@ -239,3 +242,34 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False):
     graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
     return BprStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
                                  float(lambda_reg), users, pos, neg, n_e0, *tensors)
+
+
+def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True):
+    """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
+    epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
+    batch
+
+        optimizer.zero_grad(); loss = model.bpr_step(adj, users, pos, neg, lambda_reg)
+        loss.backward(); optimizer.step()
+
+    on views of that draw. Returns the per-batch losses as one tensor on the adjacency's device
+    (empty for a sampler without interactions); nothing is read back inside the loop. A sample
+    whose user has no free item carries neg = -1: on a HIP device bpr_step skips it
+    (sampler.unsampled counts them); on a CPU adjacency, where the reference's own indexing would
+    take -1 for the last item, it raises before the first optimizer step."""
+    if sampler.device != adj.device:
+        raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
+    batches = sampler.epoch(epoch, batch_size, shuffle=shuffle)  # the draw is made here
+    if adj.device.type != "cuda" and int(sampler.unsampled.item()):
+        raise engine.LgcnError("bpr_epoch: a user has every item as a positive (no negative to "
+                               "draw); the CPU route cannot skip the sample")
+    losses = []
+    for users, pos, neg in batches:
+        optimizer.zero_grad()
+        loss = model.bpr_step(adj, users, pos, neg, lambda_reg)
+        loss.backward()
+        optimizer.step()
+        losses.append(loss.detach())
+    if not losses:
+        return torch.empty(0, dtype=torch.float32, device=adj.device)
+    return torch.stack(losses)

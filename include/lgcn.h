@@ -44,8 +44,9 @@ extern "C" {
 #endif
 
 /* 14 since the sided propagation; the training-step entry points (lgcn_bpr_loss_indexed,
- * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) were added without a bump: purely additive,
- * no existing symbol, struct or constant changed. */
+ * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) and the sampler (lgcn_bpr_sample,
+ * LGCN_TUNE_SAMPLE_BLOCKS) were added without a bump: purely additive, no existing symbol, struct
+ * or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -255,6 +256,9 @@ const char* lgcn_error_string(int code);
                                        shift: (hi - lo) >> shift + base (default 128 << 4 | 4;
                                        A/B at C3: 3,256 / 2,256 / 3,1024 / 2,2048 within noise);
                                        results identical for every value (prediction only) */
+#define LGCN_TUNE_SAMPLE_BLOCKS  7  /* lgcn_bpr_sample: the most blocks (of 256 slots per pass) its
+                                       grid-stride launch uses (0 = auto = 8 per CU); a draw never
+                                       depends on the launch geometry */
 int lgcn_tune(int knob, int value);
 
 /* device properties the host side needs (CU count); returns 0/hipError */
@@ -668,6 +672,44 @@ int lgcn_rows_scatter(const int32_t* keys_sorted, const int32_t* perm, int32_t n
 int lgcn_rows_clear(const int32_t* keys_sorted, int32_t n, int32_t row_lo, int32_t row_hi,
                     float* dst, int64_t ld_dst, int32_t d, uint32_t* mask, int32_t* count,
                     void* stream);
+
+/* ---- BPR negative sampler (main.py:349-363, BPRDataset.__getitem__) -------------------------- */
+/* The triples of `count` training samples in one launch (count may be a whole epoch). Output slot
+ * s in [0, count) takes interaction idx = order ? order[first + s] : first + s (order: device
+ * int64 with at least first + count entries, e.g. a permutation; NULL = identity) and writes
+ *   users[s] = inter_user[idx], pos[s] = inter_item[idx], neg[s] = the draw below
+ * (inter_user / inter_item: the int32 [n_inter] train interactions, duplicates kept as samples;
+ * users / pos / neg: int64 [count], what lgcn_bpr_loss_indexed and lgcn_bpr_keys take).
+ *
+ * The draw. The negative of an interaction is a pure function of (seed, epoch, idx, the user's
+ * positive list, n_items): it does not depend on batch size, order, first / count, the launch
+ * geometry (LGCN_TUNE_SAMPLE_BLOCKS) or the device.
+ *  - Positives: pos_rowptr [n_users + 1] / pos_items, int32: per user the sorted, de-duplicated
+ *    items of its interactions (the CSR lgcn_score_topk masks with: mask_rowptr / mask_items).
+ *    L = the user's list, deg its length.
+ *  - Random bits: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 /
+ *    0xBB67AE85) of counter (idx_lo32, idx_hi32, epoch, 0) under key (seed_lo32, seed_hi32);
+ *    r64 = (out[1] << 32) | out[0].
+ *  - Range: n_free = n_items - deg, j = the high 64 bits of r64 * n_free (no modulo, no
+ *    rejection loop).
+ *  - Selection: the j-th (0-based) item not in L: m = the number of positions t with
+ *    L[t] - t <= j (L[t] - t is non-decreasing: an upper-bound binary search), neg = j + m.
+ *    Uniform over the complement of L up to the 2^-33 bias of the range reduction.
+ *  - n_free <= 0 (a user with every item as a positive — the reference's rejection loop never
+ *    returns): neg = -1 and *n_unsampled (device int32, NULL = not counted; the caller zeroes it)
+ *    is incremented by an integer atomic. lgcn_bpr_loss_indexed and lgcn_bpr_keys skip a sample
+ *    whose index lies outside its table, so such a triple goes through a training step as a
+ *    sample with zero loss terms and zero gradient rows (the batch mean still divides by B).
+ * Memory safety: idx outside [0, n_inter) or inter_user[idx] outside [0, n_users) writes -1 to
+ * all three outputs of the slot and dereferences nothing further (not counted in *n_unsampled);
+ * pos_rowptr must be a CSR over pos_items. Refused on the host (LGCN_EINVAL): a NULL pointer
+ * other than order / n_unsampled / stream, n_inter / n_users / n_items < 0 or >= 2^31, first < 0,
+ * count < 0. count == 0 returns 0 and launches nothing. */
+int lgcn_bpr_sample(const int32_t* inter_user, const int32_t* inter_item, int64_t n_inter,
+                    const int64_t* order, int64_t first, int64_t count,
+                    const int32_t* pos_rowptr, const int32_t* pos_items, int64_t n_users,
+                    int64_t n_items, uint64_t seed, uint32_t epoch, int64_t* users, int64_t* pos,
+                    int64_t* neg, int32_t* n_unsampled, void* stream);
 
 /* ---- LightGCN_Fusion item pre-layer (models/lightgcn_fusion.py:45-49) ------------------------ */
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,

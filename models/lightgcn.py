@@ -118,6 +118,12 @@ class LightGCN(nn.Module):
         route, to the bit (train.bpr_step)."""
         return train.bpr_step(self, adj, users, pos, neg, lambda_reg)
 
+    def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True):
+        """One epoch of bpr_step batches over one device-side draw of the sampler
+        (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop."""
+        return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
+                               shuffle=shuffle)
+
     # -- LightGCN-style accessor (north_star "computer()") --------------------------------------
     def set_graph(self, adj_mat):
         self._graph_adj = adj_mat

@@ -1,0 +1,154 @@
+#!/usr/bin/env python
+"""Time the BPR sampler three ways in one process, on bench.py's C3 interactions (power-law,
+29.5M samples):
+
+  * device: one whole-epoch BprSampler.draw (one lgcn_bpr_sample launch) between events on the
+    current stream, median of --reps, for the identity order and for epoch()'s shuffled order
+    (the permutation made beforehand; torch.randperm is timed on its own);
+  * cpu: the same draw on the numpy path (one whole epoch, wall clock);
+  * python_loop: what BPRDataset.__getitem__ does per sample — look up the user's item set, draw
+    random.randint until the item is not in it — as a plain Python loop over the first --subset
+    interactions, extrapolated to the epoch (the DataLoader, collation and the per-batch upload
+    it sits behind are not counted).
+
+The first --check slots of the device draw are compared with the numpy path (same bits). Prints
+one JSON line on stdout (progress goes to stderr); `vs_parent_step` states the whole-epoch draw
+against one training step of the commit before the sampler (profiles/bpr_step_c3.log).
+
+    timeout -k 10 840 python tools/sampler_bench.py [--config c3] [--reps 7] [--subset 200000]
+
+One process, so the three figures come from one machine in one run; it holds the GPU for the
+whole of it and is therefore started under a time limit of its own, as every GPU step is.
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402  (CONFIGS, log: the shapes bench.py times)
+from gcn_recommendation_amd import engine, graph, sampler  # noqa: E402
+from gcn_recommendation_amd.evaluate import mask_csr  # noqa: E402
+
+PARENT_STEP_MS = 38.947  # profiles/bpr_step_c3.log: step_ms_adam_default.bpr_step
+
+
+def device_ms(fn, reps):
+    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(e))
+    return out
+
+
+def python_loop(users, items, rowptr, pos_items, n_items, subset):
+    """The reference's per-sample work, written out: returns seconds per sample."""
+    sub_u = users[:subset].tolist()
+    sub_i = items[:subset].tolist()
+    sets = {u: set(pos_items[rowptr[u]:rowptr[u + 1]].tolist()) for u in set(sub_u)}
+    rnd = random.Random(0)
+    hi = n_items - 1
+    out = [None] * len(sub_u)
+    t0 = time.perf_counter()
+    for k in range(len(sub_u)):
+        u = sub_u[k]
+        seen = sets[u]
+        neg = rnd.randint(0, hi)
+        while neg in seen:
+            neg = rnd.randint(0, hi)
+        out[k] = (u, sub_i[k], neg)
+    return (time.perf_counter() - t0) / max(len(sub_u), 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--subset", type=int, default=200_000)
+    ap.add_argument("--check", type=int, default=1_000_000)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("sampler_bench: needs a HIP device")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    engine.load_library()
+    cfg = bench.CONFIGS[args.config]
+    U, I, E = cfg["users"], cfg["items"], cfg["interactions"]
+    t0 = time.perf_counter()
+    users, items = graph.powerlaw_interactions(U, I, E, cfg["seed"])
+    bench.log(f"[sampler_bench] {E:,} interactions in {time.perf_counter() - t0:.1f}s")
+
+    t0 = time.perf_counter()
+    s = sampler.BprSampler(users, items, U, I, dev, seed=args.seed)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
+    bench.log(f"[sampler_bench] device sampler built in {build_s:.1f}s")
+    epoch = 1
+    s.draw(epoch)  # warm-up
+    perm = s.permutation(epoch)
+    s.draw(epoch, perm)
+    ident = device_ms(lambda: s.draw(epoch), args.reps)
+    shuf = device_ms(lambda: s.draw(epoch, perm), args.reps)
+    rperm = device_ms(lambda: s.permutation(epoch), args.reps)
+    got = [t[:args.check].cpu().numpy() for t in s.draw(epoch, perm)]
+    unsampled = int(s.unsampled.item())
+    bench.log(f"[sampler_bench] device draw {np.median(ident):.3f} ms identity, "
+              f"{np.median(shuf):.3f} ms shuffled")
+
+    c = sampler.BprSampler(users, items, U, I, "cpu", seed=args.seed)
+    t0 = time.perf_counter()
+    cu, cp, cn = c.draw(epoch)
+    cpu_s = time.perf_counter() - t0
+    bench.log(f"[sampler_bench] numpy draw {cpu_s:.2f}s")
+    order = perm[:args.check].cpu()
+    same = all(np.array_equal(g, w[order].numpy()) for g, w in zip(got, (cu, cp, cn)))
+    assert same, "device draw differs from the numpy path"
+    del cu, cp, cn
+
+    rowptr, pos_items = mask_csr(users, items, U)
+    per_sample = python_loop(users, items, rowptr, pos_items, I, min(args.subset, E))
+    bench.log(f"[sampler_bench] python loop {per_sample * 1e6:.3f} us per sample")
+
+    draw_ms = float(np.median(shuf))
+    result = {
+        "config": cfg["name"], "interactions": E, "users": U, "items": I,
+        "positives": int(pos_items.shape[0]), "unsampled": unsampled, "reps": args.reps,
+        "device_draw_ms": {"identity": round(float(np.median(ident)), 3),
+                           "shuffled": round(draw_ms, 3),
+                           "identity_all": [round(x, 3) for x in ident],
+                           "shuffled_all": [round(x, 3) for x in shuf]},
+        "device_randperm_ms": round(float(np.median(rperm)), 3),
+        "device_ns_per_sample": round(draw_ms * 1e6 / E, 3),
+        "sampler_build_s": round(build_s, 2),
+        "cpu_numpy_draw_s": round(cpu_s, 3),
+        "python_loop": {"subset": min(args.subset, E), "us_per_sample": round(per_sample * 1e6, 3),
+                        "epoch_s_extrapolated": round(per_sample * E, 1)},
+        "device_equals_numpy_first_slots": args.check,
+        "vs_parent_step": {"parent_step_ms": PARENT_STEP_MS,
+                           "epoch_draw_plus_randperm_ms": round(draw_ms + float(np.median(rperm)),
+                                                                3),
+                           "draw_below_one_step": bool(draw_ms < PARENT_STEP_MS)},
+        "what": ("one whole-epoch BprSampler.draw between events (median of reps; shuffled = "
+                 "order from torch.randperm, made beforehand and timed on its own); "
+                 "cpu_numpy_draw_s = the same draw on the numpy path, wall clock; python_loop = "
+                 "set lookup + random.randint until not in the set, per sample, on a subset, "
+                 "extrapolated to the epoch"),
+    }
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
