@@ -9,7 +9,8 @@
 //    item table is read once per 128 users; grid = user tiles x item splits;
 //  * top-K: a lane keeps the current K-th best score of its 16 users in registers; only scores
 //    above it are candidates (after the first few tiles, ~K·ln(items/K) per user in total): the
-//    train-item mask is a binary search in the user's sorted list, done for candidates only;
+//    train-item mask is a binary search in the user's sorted list, done for candidates only
+//    (every item is a candidate while the K-th best is below -1e10: masking raises such a score);
 //    candidates go to a per-user LDS buffer (capacity 64); users whose buffer passes 32 are
 //    compacted to their K best by rank counting under the total order (score desc, index asc):
 //    deterministic regardless of LDS arrival order;
@@ -81,7 +82,10 @@ __device__ void compact_user(WaveState& st, int u, int K, int lane) {
     if (lane == 0) {
         const int keep = n < K ? n : K;
         st.cnt[u] = keep;
-        st.thr[u] = keep == K ? st.score[u][K - 1] : -INFINITY;
+        // the candidate filter compares raw scores, and masking raises a raw score below -1e10:
+        // no threshold while the K-th best is below -1e10 (every item stays a candidate)
+        const float kth = keep == K ? st.score[u][K - 1] : -INFINITY;
+        st.thr[u] = kth < kMasked ? -INFINITY : kth;
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(kLgkm0);
@@ -260,8 +264,10 @@ extern "C" {
 
 int lgcn_eval_splits(int32_t n_users, int32_t n_items, int32_t n_cu) {
     // enough (user tile x split) blocks for ~2 per CU, splits of >= 2048 items, <= 256 splits
-    const int64_t tiles = ((int64_t)n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
-    int64_t s = (2LL * (n_cu > 0 ? n_cu : 256) + tiles - 1) / (tiles > 0 ? tiles : 1);
+    // (no users count as one tile: the answer never grows with n_users)
+    int64_t tiles = ((int64_t)n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
+    if (tiles < 1) tiles = 1;
+    int64_t s = (2LL * (n_cu > 0 ? n_cu : 256) + tiles - 1) / tiles;
     const int64_t max_by_len = ((int64_t)n_items + 2047) / 2048;
     if (s > max_by_len) s = max_by_len;
     if (s > 256) s = 256;

@@ -731,7 +731,10 @@ int lgcn_eval_splits(int32_t n_users, int32_t n_items, int32_t n_cu);
  * an ordered fmaf chain), items of user u listed in mask_items[mask_rowptr[u]:mask_rowptr[u+1]]
  * (sorted ascending) score -1e10, ties broken by lower item index. Outputs top_scores/top_idx
  * [n_users x k] in rank order (-inf / -1 past n_items). d in {32, 64, 128, 256}, k in [1, 32], 16-B
- * aligned rows. part_scores/part_idx: scratch [n_splits x n_users x k]. */
+ * aligned rows. part_scores/part_idx: scratch [n_splits x n_users x k]. -1e10 is a value, not a
+ * sentinel: an unmasked item scoring below it ranks after the masked ones. The sizes and the
+ * alignment are checked first; then n_users == 0 returns 0 and touches no pointer (all may be
+ * NULL); otherwise every pointer must be non-NULL, except mask_items when every list is empty. */
 int lgcn_score_topk(const float* user_emb, int64_t ld_u, const int32_t* users, int32_t n_users,
                     const float* item_emb, int64_t ld_i, int32_t n_items, int32_t d,
                     const int32_t* mask_rowptr, const int32_t* mask_items, int32_t k,

@@ -1,0 +1,590 @@
+"""The fused evaluation kernel lgcn_score_topk (gcn_recommendation_amd/csrc/lgcn_eval.hip: MFMA
+score tile, lazy train-item mask, per-user LDS candidate buffers with rank-counting compaction,
+cross-split merge) against tests/util.py's numpy reference: all scores in float64, masked pairs
+at fp32(-1e10), the first k under include/lgcn.h's total order (score descending, item index
+ascending).
+
+A. Exact inputs (small multiples of a power of two: every dot product is exact in fp32 in any
+   summation order, ties are plentiful): the reference is the unique right answer and top_idx /
+   top_scores must equal it BITWISE for every user and rank. Each test first asserts that its
+   float64 scores survive an fp32 round trip.
+B. Gaussian inputs: scores are rounded, so every user's list is held to the reference within the
+   standard dot-product bound tau(u, j) = gamma_d · sum_i |u_i·v_i|, gamma_d = d·2^-24 /
+   (1 - d·2^-24) (any summation order) and to nothing wider; split count, user order and
+   repetition must not change a bit.
+C. evaluate.topk_torch / recall_ndcg / evaluate agree with the reference lists scored by hand.
+
+The kernel is called through the C ABI (engine.load_library()), which lets a test choose
+n_splits, ld_u and ld_i; evaluate.topk_fused fixes all three and is covered at the end."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from gcn_recommendation_amd import engine, evaluate as E
+from util import MASKED, masked_scores64, topk_total_order
+
+pytestmark = pytest.mark.gpu
+
+
+# ----------------------------------------------------------------------------------------------
+# helpers
+# ----------------------------------------------------------------------------------------------
+def _few_bits(rng, n, d, lim=4, den=8.0):
+    """Integers in [-lim, lim] / den as fp32 (tests/test_gpu_exact.py's "few_bits")."""
+    return (rng.integers(-lim, lim + 1, (n, d)) / den).astype(np.float32)
+
+
+def _random_mask(rng, n_users, n_items, per_user=4):
+    n = per_user * n_users
+    return E.mask_csr(rng.integers(0, n_users, n), rng.integers(0, n_items, n), n_users)
+
+
+def _dev(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _score_topk(dev, ue, ie, users, mrow, mit, k, n_splits, n_items=None):
+    """lgcn_score_topk through the C ABI on device tensors ue / ie (row views allowed: their
+    row strides are ld_u / ld_i). Every output and scratch element starts as a poison value, so
+    anything the kernel leaves unwritten shows. Returns host (top_scores, top_idx)."""
+    lib = engine.load_library()
+    d = ie.shape[1]
+    assert ue.shape[1] == d and ue.stride(1) == 1 and ie.stride(1) == 1
+    n_items = ie.shape[0] if n_items is None else n_items
+    users_t = _dev(np.asarray(users, dtype=np.int32), dev)
+    n = int(users_t.numel())
+    mrow_t = _dev(np.asarray(mrow, dtype=np.int32), dev)
+    mit_t = _dev(np.asarray(mit, dtype=np.int32), dev) if len(mit) else \
+        torch.zeros(1, dtype=torch.int32, device=dev)
+    part_s = torch.full((n_splits, n, k), float("nan"), dtype=torch.float32, device=dev)
+    part_i = torch.full((n_splits, n, k), -7, dtype=torch.int32, device=dev)
+    top_s = torch.full((n, k), float("nan"), dtype=torch.float32, device=dev)
+    top_i = torch.full((n, k), -7, dtype=torch.int32, device=dev)
+    P = engine._ptr
+    with torch.cuda.device(dev):
+        rc = lib.lgcn_score_topk(P(ue), ue.stride(0), P(users_t), n, P(ie), ie.stride(0),
+                                 n_items, d, P(mrow_t), P(mit_t), k, n_splits, P(part_s),
+                                 P(part_i), P(top_s), P(top_i), engine._stream(dev))
+        assert rc == 0, rc
+        torch.cuda.synchronize(dev)
+    return top_s.cpu().numpy(), top_i.cpu().numpy()
+
+
+def _assert_exact(scores64):
+    """The premise of part A: every score is an fp32 number (so, with the inputs' few bits, is
+    every partial sum in any order: the reference is the one right answer)."""
+    assert np.array_equal(scores64.astype(np.float32).astype(np.float64), scores64)
+
+
+def _assert_bitwise(got, ref, what=""):
+    """got: the kernel's (scores fp32, idx int32); ref: the reference's (float64, int64)."""
+    (gs, gi), (rs, ri) = got, ref
+    assert gs.dtype == np.float32 and gi.dtype == np.int32
+    assert gs.shape == rs.shape and gi.shape == ri.shape
+    want_s = rs.astype(np.float32) + np.float32(0)  # an exact zero score is +0 (the sum starts there)
+    bad = np.nonzero((gi != ri).any(1) | (gs.view(np.uint32) != want_s.view(np.uint32)).any(1))[0]
+    assert bad.size == 0, (f"{what}: {bad.size} of {len(gi)} rows differ, first row {bad[0]}:\n"
+                           f"got  {gi[bad[0]].tolist()}\n     {gs[bad[0]].tolist()}\n"
+                           f"want {ri[bad[0]].tolist()}\n     {want_s[bad[0]].tolist()}")
+    assert np.array_equal(gi, ri) and np.array_equal(gs.view(np.uint32), want_s.view(np.uint32))
+
+
+def _check_exact(dev, ue, ie, users, mrow, mit, k, n_splits, what=""):
+    """One exact case end to end; returns the kernel's output and the reference's."""
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    _assert_exact(full)
+    ref = topk_total_order(full, k)
+    got = _score_topk(dev, _dev(ue, dev), _dev(ie, dev), users, mrow, mit, k, n_splits)
+    _assert_bitwise(got, ref, what)
+    return got, ref
+
+
+# ----------------------------------------------------------------------------------------------
+# A1. widths and k
+# ----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _widths_case(d):
+    rng = np.random.default_rng(100 + d)
+    n_table, n_items = 200, 2100
+    ue, ie = _few_bits(rng, n_table, d), _few_bits(rng, n_items, d)
+    users = rng.permutation(n_table)[:150]
+    mrow, mit = _random_mask(rng, n_table, n_items)
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    full.setflags(write=False)
+    first = topk_total_order(full, 33)[0]  # ties are what this input is for
+    assert (first[:, :-1] == first[:, 1:]).any(1).mean() > 0.9
+    return ue, ie, users, mrow, mit, full
+
+
+@pytest.mark.parametrize("n_splits", [1, 3])
+@pytest.mark.parametrize("k", [1, 2, 20, 31, 32])
+@pytest.mark.parametrize("d", [32, 64, 128, 256])
+def test_exact_widths_and_k(gpu_device, d, k, n_splits):
+    ue, ie, users, mrow, mit, full = _widths_case(d)
+    _assert_exact(full)
+    got = _score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit, k,
+                      n_splits)
+    _assert_bitwise(got, topk_total_order(full, k), f"d={d} k={k} splits={n_splits}")
+
+
+# ----------------------------------------------------------------------------------------------
+# A2. split geometry: short last split, empty trailing splits, fewer than k items in all
+# ----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _geometry_tables():
+    rng = np.random.default_rng(7)
+    return _few_bits(rng, 40, 64), _few_bits(rng, 2049, 64), rng.permutation(40)[:37]
+
+
+@pytest.mark.parametrize("n_splits", [1, 2, 5, 256])
+@pytest.mark.parametrize("n_items", [1, 19, 20, 31, 32, 33, 2049])
+def test_exact_split_geometry(gpu_device, n_items, n_splits):
+    ue, ie, users = _geometry_tables()
+    k = 20
+    mrow, mit = _random_mask(np.random.default_rng(n_items), 40, n_items, 2 if n_items > 1 else 1)
+    (gs, gi), _ = _check_exact(gpu_device, ue, ie[:n_items], users, mrow, mit, k, n_splits,
+                               f"items={n_items} splits={n_splits}")
+    if n_items < k:  # the tail past the last item
+        assert (gi[:, n_items:] == -1).all() and np.isneginf(gs[:, n_items:]).all()
+        assert (np.sort(gi[:, :n_items], 1) == np.arange(n_items)).all()
+
+
+def test_exact_most_splits_at_largest_k(gpu_device):
+    """Both limits of the merge at once: 256 splits x k = 32 candidates per user."""
+    ue, ie, users = _geometry_tables()
+    mrow, mit = _random_mask(np.random.default_rng(1), 40, 2049)
+    _check_exact(gpu_device, ue, ie, users, mrow, mit, 32, 256)
+
+
+@pytest.mark.parametrize("n_splits", [1, 4])
+def test_no_items_at_all(gpu_device, n_splits):
+    ue, _, _ = _geometry_tables()
+    ie = torch.zeros((1, 64), device=gpu_device)  # a table to point at; none of it is an item
+    mrow = np.zeros(41, np.int32)
+    for users in ([3], [5, 0, 5]):
+        gs, gi = _score_topk(gpu_device, _dev(ue, gpu_device), ie, users, mrow, [], 20, n_splits,
+                             n_items=0)
+        assert gi.shape == (len(users), 20) and (gi == -1).all() and np.isneginf(gs).all()
+
+
+# ----------------------------------------------------------------------------------------------
+# A3. user geometry: wave (32) and block (128) boundaries, unsorted and repeated ids
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_splits", [1, 2])
+@pytest.mark.parametrize("n_users", [1, 31, 32, 33, 127, 128, 129])
+def test_exact_user_geometry(gpu_device, n_users, n_splits):
+    rng = np.random.default_rng(21)
+    ue, ie = _few_bits(rng, 60, 64), _few_bits(rng, 700, 64)
+    mrow, mit = _random_mask(rng, 60, 700)
+    users = np.random.default_rng(n_users).integers(0, 60, n_users)
+    if n_users > 1:
+        users[-1] = users[0]  # a repeat across the batch's two ends (other waves / blocks)
+        assert (np.diff(users) < 0).any()
+    (gs, gi), _ = _check_exact(gpu_device, ue, ie, users, mrow, mit, 20, n_splits,
+                               f"users={n_users} splits={n_splits}")
+    first = {}
+    for b, u in enumerate(users.tolist()):  # a repeated id gives identical rows
+        b0 = first.setdefault(u, b)
+        assert np.array_equal(gi[b], gi[b0]) and np.array_equal(gs[b].view(np.uint32),
+                                                                gs[b0].view(np.uint32))
+    assert n_users < 31 or len(first) < n_users
+
+
+# ----------------------------------------------------------------------------------------------
+# A4. all scores equal: the order is the index order alone
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_splits", [1, 3, 7])
+def test_exact_all_scores_equal(gpu_device, n_splits):
+    n_users, n_items, d, k = 40, 2100, 64, 20
+    ue = np.full((n_users, d), 0.5, np.float32)
+    ie = np.full((n_items, d), 0.5, np.float32)
+    lowest = [(u % 4) * 23 for u in range(n_users)]  # user u's train items: 0 .. lowest[u]-1
+    mrow, mit = E.mask_csr(np.repeat(np.arange(n_users), lowest),
+                           np.concatenate([np.arange(m) for m in lowest]), n_users)
+    users = np.arange(n_users)[::-1].copy()
+    (gs, gi), _ = _check_exact(gpu_device, ue, ie, users, mrow, mit, k, n_splits)
+    for b, u in enumerate(users):
+        assert gi[b].tolist() == list(range(lowest[u], lowest[u] + k)), u  # 0..k-1, or the next k
+    assert (gs == np.float32(d * 0.25)).all()
+
+
+# ----------------------------------------------------------------------------------------------
+# A5. scores rising with the item index: every tile is 32 new candidates for every user, the
+#     compaction's worst case (k = 32: a buffer goes 32 -> 64 = its capacity on every tile)
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_splits", [1, 3])
+@pytest.mark.parametrize("k", [1, 32])
+@pytest.mark.parametrize("direction", ["rising", "falling", "mixed"])
+def test_exact_monotone_scores(gpu_device, direction, k, n_splits):
+    rng = np.random.default_rng(33)
+    n_users, n_items, d, f = 70, 1300, 64, 5
+    assert n_items % 32
+    ie = np.zeros((n_items, d), np.float32)
+    ie[:, f] = np.arange(n_items) * 2.0 ** -4          # item j scores j/16 per unit of u[f]
+    ue = _few_bits(rng, n_users, d)                    # (the other features meet zeros)
+    sign = {"rising": np.ones(n_users), "falling": -np.ones(n_users),
+            "mixed": np.where(np.arange(n_users) % 2, 1.0, -1.0)}[direction]
+    ue[:, f] = sign * (1 + np.arange(n_users) % 3)
+    mu, mi = rng.integers(0, n_users, 200), rng.integers(0, n_items, 200)
+    # and the first and last five items (the best, in either direction) for users 0 and 1
+    ends = np.concatenate([np.arange(5), n_items - 1 - np.arange(5)])
+    mu = np.concatenate([mu, np.zeros(10, np.int64), np.ones(10, np.int64)])
+    mi = np.concatenate([mi, ends, ends])
+    mrow, mit = E.mask_csr(mu, mi, n_users)
+    users = rng.permutation(n_users)
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    unmasked = full != MASKED
+    for b in range(n_users):  # strictly monotone in the item index, as announced
+        step = np.diff(full[b][unmasked[b]])
+        assert (step > 0).all() if sign[users[b]] > 0 else (step < 0).all()
+    _check_exact(gpu_device, ue, ie, users, mrow, mit, k, n_splits, f"{direction} k={k}")
+
+
+# ----------------------------------------------------------------------------------------------
+# A6. mask edges
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_splits", [1, 2])
+def test_exact_mask_edges(gpu_device, n_splits):
+    rng = np.random.default_rng(44)
+    n_users, n_items, d, k = 7, 300, 64, 20
+    split0 = 160  # two splits of 300 items: ceil(300 / 2) rounded up to the 32-item tile
+    ue, ie = _few_bits(rng, n_users, d), _few_bits(rng, n_items, d)
+    # item 0 is user 5's single best item and the last item user 6's (|item features| <= 1/2)
+    ie[0] = np.where(ue[5] < 0, -0.5, 0.5)
+    ie[-1] = np.where(ue[6] < 0, -0.5, 0.5)
+    nothing = E.mask_csr([], [], n_users)
+    free = masked_scores64(ue, ie, np.arange(n_users), *nothing)
+    free_s, free_i = topk_total_order(free, 2 * k)  # every user's order with nothing masked
+    assert free_i[5, 0] == 0 and free_s[5, 0] > free_s[5, 1]
+    assert free_i[6, 0] == n_items - 1 and free_s[6, 0] > free_s[6, 1]
+    kept = np.sort(rng.permutation(n_items)[:k - 1])
+    lists = {0: [],                                          # no train item
+             1: np.arange(n_items),                          # every item
+             2: np.setdiff1d(np.arange(n_items), kept),      # all but k - 1
+             3: np.arange(split0),                           # all of split 0, none of split 1
+             4: free_i[4, :k],                               # exactly its current top k
+             5: [0],                                         # item 0 alone
+             6: [n_items - 1]}                               # the last item alone
+    mrow, mit = E.mask_csr(np.concatenate([np.full(len(v), u) for u, v in lists.items()]),
+                           np.concatenate([np.asarray(v, np.int64) for v in lists.values()]),
+                           n_users)
+    users = np.arange(n_users)
+    (gs, gi), _ = _check_exact(gpu_device, ue, ie, users, mrow, mit, k, n_splits)
+    # each list once more, in words of its own (all implied by the reference, all equalities)
+    assert np.array_equal(gi[0], free_i[0, :k])
+    assert gi[1].tolist() == list(range(k)) and (gs[1] == np.float32(-1e10)).all()
+    # k - 1 unmasked items, then the tail: the lowest masked index at -1e10
+    assert sorted(gi[2, :k - 1].tolist()) == kept.tolist()
+    assert gi[2, k - 1] == np.setdiff1d(np.arange(n_items), kept)[0] and gs[2, k - 1] == -1e10
+    # the order of split 1's items alone
+    assert np.array_equal(gi[3], topk_total_order(free[3:4, split0:], k)[1][0] + split0)
+    # the next k after the masked top k; the same list without its head
+    assert np.array_equal(gi[4], free_i[4, k:])
+    assert np.array_equal(gi[5], free_i[5, 1:k + 1]) and np.array_equal(gi[6], free_i[6, 1:k + 1])
+
+
+# ----------------------------------------------------------------------------------------------
+# A7. -1e10 is a value: unmasked items scoring below it rank after the masked ones
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_splits", [1, 2])
+def test_exact_scores_below_the_mask_value(gpu_device, n_splits):
+    rng = np.random.default_rng(55)
+    n_users, n_items, d, k = 33, 48, 32, 32
+    vals = np.array([0, 0, 0, 2.0 ** 16, -2.0 ** 16, 2.0 ** 17, -2.0 ** 17], np.float32)
+    ue, ie = rng.choice(vals, (n_users, d)), rng.choice(vals, (n_items, d))
+    # user 0 · item j = -2^34, -2^33, 0, -2^34 for j % 4 = 0, 1, 2, 3
+    ue[0] = 0
+    ue[0, 0] = -2.0 ** 17
+    ie[:, 0] = np.tile(np.array([2.0 ** 17, 2.0 ** 16, 0, 2.0 ** 17], np.float32), n_items // 4)
+    mu, mi = rng.integers(0, n_users, 250), rng.integers(0, n_items, 250)
+    keep = mu != 0
+    mrow, mit = E.mask_csr(np.concatenate([mu[keep], np.zeros(6, np.int64)]),
+                           np.concatenate([mi[keep], [1, 2, 4, 10, 40, 47]]), n_users)
+    users = np.arange(n_users)
+    (gs, gi), (rs, ri) = _check_exact(gpu_device, ue, ie, users, mrow, mit, k, n_splits)
+    assert -2.0 ** 34 < MASKED < -2.0 ** 33
+    # user 0: 10 zeros, 11 at -2^33, its 6 train items at -1e10 in index order, then -2^34s
+    assert gs[0].tolist() == [0.0] * 10 + [-2.0 ** 33] * 11 + [MASKED] * 6 + [-2.0 ** 34] * 5
+    assert gi[0, 21:].tolist() == [1, 2, 4, 10, 40, 47, 0, 3, 7, 8, 11]
+    # and the random users: lists that hold unmasked scores below -1e10 after masked items
+    below = (rs < MASKED).any(1) & (rs == MASKED).any(1)
+    assert below.sum() >= 5
+    for b in np.nonzero(below)[0]:  # above -1e10 | at -1e10 | below it, in that order
+        at = np.nonzero(gs[b] == np.float32(-1e10))[0]
+        assert np.array_equal(gs[b] > -1e10, np.arange(k) < at.min())
+        assert np.array_equal(gs[b] < -1e10, np.arange(k) > at.max())
+
+
+@pytest.mark.parametrize("n_splits", [1, 3])
+@pytest.mark.parametrize("k", [1, 20, 32])
+def test_exact_train_items_among_scores_below_the_mask_value(gpu_device, k, n_splits):
+    """The same promise once a user's threshold is finite: 400 items (five, five and three tiles
+    in three splits), every raw score of users 0..29 at -3·2^32, -2^34 or -5·2^32, all below
+    -1e10. After the first compaction the k-th best is below -1e10 too, and a train item met
+    later has a raw score at or below it, yet as a train item it scores -1e10 and goes first."""
+    rng = np.random.default_rng(56)
+    n_users, n_items, d = 40, 400, 32
+    ue = np.zeros((n_users, d), np.float32)
+    ie = np.zeros((n_items, d), np.float32)
+    ie[:, 0] = 2.0 ** 17
+    ie[:, 1] = rng.choice(np.array([0, 2.0 ** 16], np.float32), n_items)
+    ue[:30, 0] = -2.0 ** 17                                      # -2^34 from feature 0 ...
+    ue[:30, 1] = np.tile(np.array([-2.0 ** 16, 0, 2.0 ** 16], np.float32), 10)  # ... -, 0, + 2^32
+    ue[30:35, 0] = 2.0 ** 17                                     # all scores far above
+    ue[35:, 1] = np.array([-2.0 ** 16, 2.0 ** 16, 0, -2.0 ** 16, 2.0 ** 16])  # 0 or -+2^32
+    # train items: user u has u % 6 + (40 if u % 7 == 0) of them, none before item lo[u]
+    lo = np.array([0, 65, 130, 200, 330, 384])[np.arange(n_users) % 6]
+    count = np.arange(n_users) % 6 + np.where(np.arange(n_users) % 7 == 0, 40, 0)
+    count = np.minimum(count, n_items - lo)
+    mu = np.repeat(np.arange(n_users), count)
+    mi = np.concatenate([lo[u] + rng.permutation(n_items - lo[u])[:count[u]]
+                         for u in range(n_users)])
+    mrow, mit = E.mask_csr(mu, mi, n_users)
+    users = rng.permutation(n_users)
+    raw = masked_scores64(ue, ie, users, *E.mask_csr([], [], n_users))
+    assert (raw[users < 30] < MASKED).all() and (raw[users >= 30] > MASKED).all()
+    (gs, gi), _ = _check_exact(gpu_device, ue, ie, users, mrow, mit, k, n_splits, f"k={k}")
+    seen = 0
+    for b, u in enumerate(users):  # in words of its own: the train items first, in index order
+        if u < 30:
+            mine = mit[mrow[u]:mrow[u + 1]][:k]
+            assert np.array_equal(gi[b, :len(mine)], mine)
+            assert np.array_equal(gs[b] == np.float32(-1e10), np.arange(k) < len(mine))
+            seen += len(mine) > 0 and mine[0] >= 65
+    assert seen >= 15  # users whose first train item comes after two full tiles
+
+
+# ----------------------------------------------------------------------------------------------
+# A8. strides
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", [32, 128])
+def test_exact_row_strides(gpu_device, d):
+    """ld_u = d + 4 and ld_i = 2d: views of wider tables that hold NaN outside the view."""
+    rng = np.random.default_rng(66 + d)
+    n_table, n_items, k = 50, 777, 20
+    ue, ie = _few_bits(rng, n_table, d), _few_bits(rng, n_items, d)
+    mrow, mit = _random_mask(rng, n_table, n_items)
+    users = rng.integers(0, n_table, 45)
+    wide_u = torch.full((n_table, d + 4), float("nan"), device=gpu_device)
+    wide_i = torch.full((n_items, 2 * d), float("nan"), device=gpu_device)
+    wide_u[:, 4:] = _dev(ue, gpu_device)
+    wide_i[:, d:] = _dev(ie, gpu_device)
+    vu, vi = wide_u[:, 4:], wide_i[:, d:]
+    assert vu.stride(0) == d + 4 and vi.stride(0) == 2 * d and not vu.is_contiguous()
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    _assert_exact(full)
+    for n_splits in (1, 3):
+        got = _score_topk(gpu_device, vu, vi, users, mrow, mit, k, n_splits)
+        _assert_bitwise(got, topk_total_order(full, k), f"d={d} splits={n_splits}")
+
+
+def test_exact_tables_in_one_allocation(gpu_device):
+    """User and item tables as the two row ranges of one allocation (the models' propagated
+    table: users first, items after)."""
+    rng = np.random.default_rng(77)
+    U, I, d, k = 50, 900, 64, 20
+    table = _few_bits(rng, U + I + 30, d)  # (rows past the items: never an item)
+    mrow, mit = _random_mask(rng, U, I)
+    users = rng.permutation(U)
+    full = masked_scores64(table[:U], table[U:U + I], users, mrow, mit)
+    _assert_exact(full)
+    t = _dev(table, gpu_device)
+    for n_splits in (1, 2):
+        got = _score_topk(gpu_device, t[:U], t[U:], users, mrow, mit, k, n_splits, n_items=I)
+        _assert_bitwise(got, topk_total_order(full, k), f"splits={n_splits}")
+
+
+# ----------------------------------------------------------------------------------------------
+# B. Gaussian inputs
+# ----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _gauss_case(d):
+    rng = np.random.default_rng(900 + d)
+    n_table, n_items = 350, 4000
+    ue = rng.standard_normal((n_table, d)).astype(np.float32)
+    ie = rng.standard_normal((n_items, d)).astype(np.float32)
+    mrow, mit = _random_mask(rng, n_table, n_items, 10)
+    users = rng.permutation(n_table)[:300]
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    masked = np.zeros(full.shape, bool)
+    for b, u in enumerate(users):
+        masked[b, mit[mrow[u]:mrow[u + 1]]] = True
+    gamma = d * 2.0 ** -24 / (1 - d * 2.0 ** -24)
+    tau = gamma * (np.abs(ue.astype(np.float64))[users] @ np.abs(ie.astype(np.float64)).T)
+    tau[masked] = 0.0  # a masked pair's score is the constant -1e10: nothing is rounded
+    for a in (full, masked, tau):
+        a.setflags(write=False)
+    return ue, ie, users, mrow, mit, full, masked, tau
+
+
+@pytest.mark.parametrize("n_splits", [1, 4])
+@pytest.mark.parametrize("d", [32, 256])
+def test_gaussian_lists_within_rounding(gpu_device, d, n_splits):
+    ue, ie, users, mrow, mit, full, masked, tau = _gauss_case(d)
+    k = 20
+    n, n_items = full.shape
+    assert (~masked).sum(1).min() >= k
+    gs, gi = _score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit,
+                         k, n_splits)
+    rows = np.arange(n)[:, None]
+    # distinct and in range
+    assert ((gi >= 0) & (gi < n_items)).all()
+    srt = np.sort(gi, 1)
+    assert (srt[:, 1:] != srt[:, :-1]).all()
+    # no masked item while k unmasked ones exist
+    assert not masked[rows, gi].any()
+    # each returned score within tau of the float64 score of its own index
+    s64 = gs.astype(np.float64)
+    own_tau = tau[rows, gi]
+    err = np.abs(s64 - full[rows, gi])
+    assert (err <= own_tau).all(), (err / own_tau).max()
+    # in the header's order by its own scores
+    a, b = gs[:, :-1], gs[:, 1:]
+    assert ((a > b) | ((a == b) & (gi[:, :-1] < gi[:, 1:]))).all()
+    # nothing left out beats the k-th place by more than the two roundings
+    left_out = np.ones(full.shape, bool)
+    left_out[rows, gi] = False
+    bound = s64[:, -1:] + tau + own_tau[:, -1:]
+    assert (full <= bound)[left_out].all(), (full - bound)[left_out].max()
+
+
+@pytest.mark.parametrize("d", [32, 256])
+def test_gaussian_bits_do_not_depend_on_splits_slots_or_runs(gpu_device, d):
+    ue, ie, users, mrow, mit = _gauss_case(d)[:5]
+    uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
+
+    def run(us, n_splits):
+        gs, gi = _score_topk(gpu_device, uet, iet, us, mrow, mit, 20, n_splits)
+        return gs.view(np.uint32), gi
+
+    s1, i1 = run(users, 1)
+    for n_splits in (4, 9, 1):  # other split counts; and the same call again
+        s, i = run(users, n_splits)
+        assert np.array_equal(s, s1) and np.array_equal(i, i1), n_splits
+    s, i = run(users, 4)
+    s4, i4 = run(users, 4)
+    assert np.array_equal(s, s4) and np.array_equal(i, i4)
+    perm = np.random.default_rng(d).permutation(len(users))  # another slot, wave and block
+    s, i = run(users[perm], 4)
+    assert np.array_equal(s, s1[perm]) and np.array_equal(i, i1[perm])
+
+
+# ----------------------------------------------------------------------------------------------
+# C. the surrounding Python
+# ----------------------------------------------------------------------------------------------
+class _Tables(torch.nn.Module):
+    """A model for evaluate.evaluate: its forward returns the two tables as they are."""
+
+    def __init__(self, ue, ie):
+        super().__init__()
+        self.ue, self.ie = ue, ie
+
+    def forward(self, adj):
+        return self.ue, self.ie, None, None, None
+
+
+def _metrics_by_hand(top, truth):
+    """The metrics on given lists: hit -> recall 1, NDCG 1 / log2(pos + 2)."""
+    hit = top == truth[:, None]
+    found, pos = hit.any(1), hit.argmax(1)
+    return float(found.mean()), float(np.where(found, 1.0 / np.log2(pos + 2), 0.0).mean())
+
+
+@pytest.mark.parametrize("d", [64, 12])
+def test_python_evaluation_agrees_with_reference_lists(gpu_device, d):
+    import pandas as pd
+    rng = np.random.default_rng(1200 + d)
+    U, I, k = 180, 1500, 20
+    lim = {64: 8, 12: 16}[d]  # coarse enough for ties at the k-th place, fine enough for none
+    ue, ie = _few_bits(rng, U, d, lim, 2.0 * lim), _few_bits(rng, I, d, lim, 2.0 * lim)
+    tu, ti = rng.integers(0, U, 6 * U), rng.integers(0, I, 6 * U)
+    mrow, mit = E.mask_csr(tu, ti, U)
+    users = rng.permutation(U)[:150]  # evaluate takes each user once (a dict)
+    full = masked_scores64(ue, ie, users, mrow, mit)
+    _assert_exact(full)
+    rs, ri = topk_total_order(full, k + 1)
+    no_tie_at_k = rs[:, k - 1] > rs[:, k]
+    no_tie = (rs[:, :-1] > rs[:, 1:]).all(1)
+    assert no_tie_at_k.sum() >= 50 and no_tie.sum() >= 8 and (~no_tie_at_k).sum() >= 8
+    rs, ri = rs[:, :k], ri[:, :k]
+    uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
+    assert E.fused_supported(d, k) == (d == 64)
+
+    # topk_torch: the reference's scores everywhere; its items where the k-th place is not tied,
+    # as a set, because torch.topk fixes no order among equal scores inside the list (a tie at
+    # places 3 and 4 may come out either way); its list, place by place, where no place is tied
+    ts, ti_ = E.topk_torch(uet, iet, users, mrow, mit, k)
+    ts, ti_ = ts.cpu().numpy(), ti_.cpu().numpy()
+    assert np.array_equal(ts.view(np.uint32),
+                          (rs.astype(np.float32) + np.float32(0)).view(np.uint32))
+    assert np.array_equal(np.sort(ti_[no_tie_at_k], 1), np.sort(ri[no_tie_at_k], 1))
+    assert np.array_equal(ti_[no_tie], ri[no_tie])
+
+    # held-out items whose position does not hang on a tie (torch.topk fixes no tie order): for
+    # every other user an item of the reference's top k whose score occurs once in the user's
+    # row, else an item strictly below the k-th score (in nobody's top k)
+    truth = np.empty(len(users), np.int64)
+    for b in range(len(users)):
+        vals, first, counts = np.unique(full[b], return_index=True, return_counts=True)
+        in_top = np.intersect1d(first[counts == 1], ri[b])
+        truth[b] = rng.choice(in_top) if b % 2 == 0 and in_top.size else \
+            rng.choice(np.nonzero(full[b] < rs[b, -1])[0])
+    want = _metrics_by_hand(ri, truth)
+    assert 0.3 < want[0] < 0.6 and 0.0 < want[1] < want[0]
+
+    # recall_ndcg reads the train items from the adjacency's CSR: user rows, item columns at U
+    t_rowptr, t_cols = mrow.astype(np.int64), mit.astype(np.int64) + U
+    for bs in (1024, 37):
+        got = E.recall_ndcg(uet, iet, users, truth, t_rowptr, t_cols, U, k=k, batch_size=bs)
+        assert got == want, (bs, got, want)
+    *got, tops = E.recall_ndcg(uet, iet, users, truth, t_rowptr, t_cols, U, k=k, batch_size=64,
+                               return_topk=True)
+    assert tuple(got) == want and np.array_equal(tops[no_tie], ri[no_tie])
+
+    # evaluate: fused at d = 64, torch ops at d = 12; one batch and several
+    model = _Tables(uet, iet)
+    val = pd.DataFrame({"user_idx": users, "item_idx": truth})
+    train = pd.DataFrame({"user_idx": tu, "item_idx": ti})
+    for bs in (8192, 37):
+        got = E.evaluate(model, val, train, None, k, gpu_device, batch_size=bs)
+        assert got == want, (bs, got, want)
+    if d == 64:  # the fused lists are the reference's, so any held-out item scores the same
+        anywhere = rng.integers(0, I, len(users))
+        val = pd.DataFrame({"user_idx": users, "item_idx": anywhere})
+        assert E.evaluate(model, val, train, None, k, gpu_device, batch_size=64) == \
+            _metrics_by_hand(ri, anywhere)
+
+
+# ----------------------------------------------------------------------------------------------
+# the wrapper evaluate.topk_fused
+# ----------------------------------------------------------------------------------------------
+def test_topk_fused_wrapper(gpu_device):
+    ue, ie, users, mrow, mit, full = _widths_case(64)
+    uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
+    for k in (1, 20, 32):
+        ref = topk_total_order(full, k)
+        for us in (users, users.astype(np.int32), users.tolist(), _dev(users, gpu_device)):
+            s, i = E.topk_fused(uet, iet, us, mrow, mit, k)
+            assert s.shape == i.shape == (len(users), k)
+            _assert_bitwise((s.cpu().numpy(), i.cpu().numpy()), ref, f"k={k}")
+    # tables that are not contiguous, device-resident mask, no train item at all
+    wide = torch.full((ue.shape[0], 2 * 64), float("nan"), device=gpu_device)
+    wide[:, :64] = uet
+    s, i = E.topk_fused(wide[:, :64], iet, users, _dev(mrow, gpu_device), _dev(mit, gpu_device))
+    _assert_bitwise((s.cpu().numpy(), i.cpu().numpy()), topk_total_order(full, 20))
+    none = E.mask_csr([], [], ue.shape[0])
+    s, i = E.topk_fused(uet, iet, users, *none, k=20)
+    _assert_bitwise((s.cpu().numpy(), i.cpu().numpy()),
+                    topk_total_order(masked_scores64(ue, ie, users, *none), 20))
+    # an empty batch
+    for empty in (np.zeros(0, np.int64), []):
+        s, i = E.topk_fused(uet, iet, empty, mrow, mit, 20)
+        assert s.shape == i.shape == (0, 20)
+        assert s.dtype == torch.float32 and i.dtype == torch.int32
+    # and what the kernel does not have is an error, not another path
+    with pytest.raises(engine.LgcnError):
+        E.topk_fused(uet, iet, users, mrow, mit, 33)
+    with pytest.raises(engine.LgcnError):
+        E.topk_fused(uet[:, :12].contiguous(), iet[:, :12].contiguous(), users, mrow, mit, 20)
