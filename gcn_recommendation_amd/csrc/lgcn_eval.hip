@@ -258,6 +258,180 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ par
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// lgcn_score_rank: the rank of one held-out item per user under the same total order, with no
+// top-K selection. Every score that enters a comparison comes from score_tile below: the MFMA
+// chain of k_score_topk's main loop (a score is a function of its (user row, item row) pair
+// alone, wherever the pair sits in a tile), so one score table explains every rank.
+//  1. k_rank_target: per 32 slots a gathered tile (column c = the target of slot c); its diagonal
+//     is score(slot, target). A train item as target scores -1e10. -> target_score
+//  2. k_rank_count: k_score_topk's tile loop without WaveState: per (lane, C-row) an integer
+//     count of raw scores that beat the target's, summed over the 32 columns -> part[split][slot]
+//  3. k_rank_finish: one wave per slot sums the parts and corrects them for the user's train
+//     items (32 per gathered tile): minus what the raw score counted, plus what -1e10 counts.
+// ---------------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ void load_row_half(const float* __restrict__ p, bool ok,
+                                              float4 (&v)[D / 8]) {
+#pragma unroll
+    for (int q = 0; q < D / 8; ++q)
+        v[q] = ok ? *reinterpret_cast<const float4*>(p + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// C[user row][item col] = the ordered fmaf chain over the features, as in k_score_topk.
+template <int D>
+__device__ __forceinline__ f32x16 score_tile(const float4 (&a)[D / 8], const float4 (&b)[D / 8]) {
+    f32x16 acc = {};
+#pragma unroll
+    for (int q = 0; q < D / 8; ++q) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+template <int D>
+__global__ __launch_bounds__(kWaves * 64) void k_rank_target(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    int32_t n_users, const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    const int32_t* __restrict__ mrow, const int32_t* __restrict__ mitems,
+    const int32_t* __restrict__ targets, float* __restrict__ target_score) {
+    constexpr int DH = D / 2;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    const int32_t slot = (blockIdx.x * kWaves + wave) * kUsersPerWave + col;
+    const bool ok = slot < n_users;
+    const int32_t u = ok ? users[slot] : 0;
+    const int32_t t = ok ? targets[slot] : -1;
+    const bool tok = t >= 0 && t < n_items;
+    float4 a[D / 8], b[D / 8];
+    load_row_half<D>(uemb + (int64_t)u * ld_u + h * DH, ok, a);
+    load_row_half<D>(iemb + (tok ? (int64_t)t * ld_i : 0) + h * DH, tok, b);
+    const f32x16 acc = score_tile<D>(a, b);
+    // the diagonal: row col of column col is register (col&3) + 4(col>>3) of half (col>>2)&1
+    const int rd = (col & 3) + 4 * (col >> 3);
+    float sc = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sc = r == rd ? acc[r] : sc;
+    if (ok && h == ((col >> 2) & 1)) {
+        if (!tok) sc = __builtin_nanf("");
+        else if (in_sorted(mitems, mrow[u], mrow[u + 1], t)) sc = kMasked;
+        target_score[slot] = sc;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(kWaves * 64, D <= 64 ? 3 : 1) void k_rank_count(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    int32_t n_users, const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    int32_t split_len, const int32_t* __restrict__ targets,
+    const float* __restrict__ target_score, int32_t* __restrict__ part) {
+    constexpr int DH = D / 2;
+    __shared__ __attribute__((aligned(16))) float s_ts[kWaves][kUsersPerWave];
+    __shared__ __attribute__((aligned(16))) int32_t s_tg[kWaves][kUsersPerWave];
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    const int32_t ub = (blockIdx.x * kWaves + wave) * kUsersPerWave;
+    const int32_t split = blockIdx.y;
+    const int32_t it0 = split * split_len;
+    const int32_t it1 = min(n_items, it0 + split_len);
+    const bool ok = ub + col < n_users;
+    if (h == 0) {  // a slot past the batch compares against NaN: it counts nothing
+        s_ts[wave][col] = ok ? target_score[ub + col] : __builtin_nanf("");
+        s_tg[wave][col] = ok ? targets[ub + col] : -1;
+    }
+    float4 a[D / 8];
+    load_row_half<D>(uemb + (ok ? (int64_t)users[ub + col] * ld_u : 0) + h * DH, ok, a);
+    __syncthreads();
+    // (the targets' scores and indices sit in LDS, as k_score_topk's thresholds do: under the
+    // launch bounds the compiler keeps them there or in registers, whichever fits 3 waves per
+    // SIMD at d <= 64)
+    int32_t cnt[16] = {};
+    float4 bcur[D / 8], bnxt[D / 8];
+    auto load_tile = [&](int32_t t0, float4 (&b)[D / 8]) {
+        const int32_t item = t0 + col;
+        const bool iok = item < it1;
+        load_row_half<D>(iemb + (iok ? (int64_t)item * ld_i : 0) + h * DH, iok, b);
+    };
+    if (it0 < it1) load_tile(it0, bcur);
+    for (int32_t t0 = it0; t0 < it1; t0 += 32) {
+        if (t0 + 32 < it1) load_tile(t0 + 32, bnxt);
+        const int32_t item = t0 + col;
+        const bool iok = item < it1;
+        const f32x16 acc = score_tile<D>(a, bcur);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 ts = *reinterpret_cast<const float4*>(&s_ts[wave][8 * g + 4 * h]);
+            const int4 tg = *reinterpret_cast<const int4*>(&s_tg[wave][8 * g + 4 * h]);
+            cnt[4 * g] += (iok && item != tg.x && better(acc[4 * g], item, ts.x, tg.x)) ? 1 : 0;
+            cnt[4 * g + 1] +=
+                (iok && item != tg.y && better(acc[4 * g + 1], item, ts.y, tg.y)) ? 1 : 0;
+            cnt[4 * g + 2] +=
+                (iok && item != tg.z && better(acc[4 * g + 2], item, ts.z, tg.z)) ? 1 : 0;
+            cnt[4 * g + 3] +=
+                (iok && item != tg.w && better(acc[4 * g + 3], item, ts.w, tg.w)) ? 1 : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < D / 8; ++q) bcur[q] = bnxt[q];
+    }
+    // the 32 columns of a row live in the 32 lanes of this half
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        int c = cnt[r];
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) c += __shfl_xor(c, off);
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (col == 0 && ub + row < n_users) part[(int64_t)split * n_users + ub + row] = c;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void k_rank_finish(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    int32_t n_users, const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    const int32_t* __restrict__ mrow, const int32_t* __restrict__ mitems,
+    const int32_t* __restrict__ targets, const float* __restrict__ target_score,
+    const int32_t* __restrict__ part, int32_t n_splits, int32_t* __restrict__ rank) {
+    constexpr int DH = D / 2;
+    const int32_t slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    const int32_t t = targets[slot];
+    if (t < 0 || t >= n_items) {  // (uniform over the wave)
+        if (lane == 0) rank[slot] = -1;
+        return;
+    }
+    const int32_t u = users[slot];
+    const float ts = target_score[slot];
+    int32_t c = 0;
+    for (int32_t s = lane; s < n_splits; s += 64) c += part[(int64_t)s * n_users + slot];
+    const int32_t lo = mrow[u], hi = mrow[u + 1];
+    if (lo < hi) {
+        float4 a[D / 8], b[D / 8];
+        load_row_half<D>(uemb + (int64_t)u * ld_u + h * DH, true, a);  // every row: this user
+        for (int32_t e0 = lo; e0 < hi; e0 += 32) {
+            const int32_t e = e0 + col;
+            const int32_t m = e < hi ? mitems[e] : -1;
+            // (an entry outside the table masks nothing; a repeated entry masks once)
+            const bool mok = m >= 0 && m < n_items && !(e > lo && mitems[e - 1] == m);
+            load_row_half<D>(iemb + (mok ? (int64_t)m * ld_i : 0) + h * DH, mok, b);
+            const f32x16 acc = score_tile<D>(a, b);
+            if (h == 0 && mok && m != t)
+                c += (better(kMasked, m, ts, t) ? 1 : 0) - (better(acc[0], m, ts, t) ? 1 : 0);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if (lane == 0) rank[slot] = c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -322,6 +496,51 @@ int lgcn_score_topk(const float* user_emb, int64_t ld_u, const int32_t* users, i
     hipLaunchKernelGGL(k_topk_merge, dim3(n_users), dim3(64), mlds, s, part_scores, part_idx,
                        n_users, n_splits, k, top_scores, top_idx);
     e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lgcn_score_rank(const float* user_emb, int64_t ld_u, const int32_t* users, int32_t n_users,
+                    const float* item_emb, int64_t ld_i, int32_t n_items, int32_t d,
+                    const int32_t* mask_rowptr, const int32_t* mask_items,
+                    const int32_t* targets, int32_t n_splits, int32_t* part, float* target_score,
+                    int32_t* rank, void* stream) {
+    if (n_users < 0 || n_items < 0 || n_splits < 1 || n_splits > 256) return LGCN_EINVAL;
+    if (d != 32 && d != 64 && d != 128 && d != 256) return LGCN_EINVAL;
+    if (ld_u % 4 || ld_i % 4 || (reinterpret_cast<uintptr_t>(user_emb) & 15) ||
+        (reinterpret_cast<uintptr_t>(item_emb) & 15))
+        return LGCN_EALIGN;
+    if (n_users == 0) return 0;
+    if (!user_emb || !users || !item_emb || !mask_rowptr || !targets || !part || !target_score ||
+        !rank)
+        return LGCN_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int32_t split_len = (int32_t)(((int64_t)n_items + n_splits - 1) / n_splits);
+    split_len = ((split_len + 31) / 32) * 32;
+    if (split_len == 0) split_len = 32;
+    const int32_t tiles = (n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
+    hipError_t e = hipSuccess;
+#define LGCN_RANK_LAUNCH(D_)                                                                      \
+    do {                                                                                          \
+        hipLaunchKernelGGL(k_rank_target<D_>, dim3(tiles), dim3(kWaves * 64), 0, s, user_emb,     \
+                           ld_u, users, n_users, item_emb, ld_i, n_items, mask_rowptr,            \
+                           mask_items, targets, target_score);                                    \
+        if ((e = hipGetLastError()) != hipSuccess) break;                                         \
+        hipLaunchKernelGGL(k_rank_count<D_>, dim3(tiles, n_splits), dim3(kWaves * 64), 0, s,      \
+                           user_emb, ld_u, users, n_users, item_emb, ld_i, n_items, split_len,    \
+                           targets, target_score, part);                                          \
+        if ((e = hipGetLastError()) != hipSuccess) break;                                         \
+        hipLaunchKernelGGL(k_rank_finish<D_>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u,      \
+                           users, n_users, item_emb, ld_i, n_items, mask_rowptr, mask_items,      \
+                           targets, target_score, part, n_splits, rank);                          \
+        e = hipGetLastError();                                                                    \
+    } while (0)
+    switch (d) {
+        case 32: LGCN_RANK_LAUNCH(32); break;
+        case 64: LGCN_RANK_LAUNCH(64); break;
+        case 128: LGCN_RANK_LAUNCH(128); break;
+        default: LGCN_RANK_LAUNCH(256); break;
+    }
+#undef LGCN_RANK_LAUNCH
     return e == hipSuccess ? 0 : (int)e;
 }
 

@@ -143,3 +143,303 @@ def evaluate(model, val_or_test_data, train_data, norm_adj_tensor, k, device, ba
     ndcg = np.where(found, 1.0 / np.log2(pos + 2), 0.0)
     return float(found.mean()) if len(found) else float("nan"), \
         float(ndcg.mean()) if len(found) else float("nan")
+
+
+# ----------------------------------------------------------------------------------------------
+# rank path: lgcn_score_rank (the held-out item's exact rank; no top-k, any k, every k at once)
+# ----------------------------------------------------------------------------------------------
+# The reference evaluates leave-one-out (one held-out item per user, main.py:406), so Recall@k and
+# NDCG@k are functions of one integer per user: the 0-based rank of the held-out item among all
+# items under include/lgcn.h's total order (score descending, item index ascending, the user's
+# train items at -1e10). Recall@k = (rank < k), NDCG@k = 1 / log2(rank + 2) when rank < k.
+_n_cu = {}
+
+
+def _device_cus(dev):
+    import ctypes
+    from . import engine
+    idx = dev.index or 0
+    if idx not in _n_cu:
+        n_cu = ctypes.c_int32(0)
+        engine._check(engine.load_library().lgcn_device_info(idx, ctypes.byref(n_cu), None),
+                      "device_info")
+        _n_cu[idx] = n_cu.value
+    return _n_cu[idx]
+
+
+def _check_tables(user_emb, item_emb):
+    from .engine import LgcnError
+    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32:
+            raise LgcnError(f"rank: {name} must be a 2-D float32 tensor")
+    if user_emb.device != item_emb.device or user_emb.shape[1] != item_emb.shape[1]:
+        raise LgcnError("rank: user_emb and item_emb must share a device and a width")
+
+
+def _index_tensor(name, a, dev):
+    """users / targets as a 1-D integer tensor on dev: a tensor must already be there (nothing is
+    moved silently), anything else is uploaded once."""
+    from .engine import LgcnError
+    if torch.is_tensor(a):
+        if a.device != dev:
+            raise LgcnError(f"rank: {name} on {a.device}, tables on {dev}")
+        if a.dtype not in (torch.int32, torch.int64):
+            raise LgcnError(f"rank: {name} must be int32 or int64, not {a.dtype}")
+    else:
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu":
+            raise LgcnError(f"rank: {name} must be integers, not {a.dtype}")
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+    if a.dim() != 1:
+        raise ValueError(f"rank: {name} must be 1-D")
+    return a
+
+
+def _mask_tensor(name, a, dev):
+    """A mask CSR array as a contiguous int32 tensor on dev: a device tensor is used as it is (no
+    upload, no copy), numpy is uploaded."""
+    from .engine import LgcnError
+    if torch.is_tensor(a):
+        if a.device != dev or a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
+            raise LgcnError(f"rank: {name} must be a contiguous 1-D int32 tensor on {dev}")
+        return a
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+
+
+def _slots(users, targets, n_table, n_items, dev):
+    """(users int32, targets int32) for the kernel: a target outside [0, n_items) becomes -1 (the
+    kernel's 'no target'), and so does the target of a user outside the table, whose id becomes 0:
+    such a slot ranks -1 and nothing of it is dereferenced. Device ops only."""
+    users = _index_tensor("users", users, dev)
+    targets = _index_tensor("targets", targets, dev)
+    if users.shape != targets.shape:
+        raise ValueError(f"rank: {users.numel()} users but {targets.numel()} targets")
+    bad_u = (users < 0) | (users >= n_table)
+    bad_t = bad_u | (targets < 0) | (targets >= n_items)
+    users = torch.where(bad_u, torch.zeros_like(users), users).to(torch.int32)
+    targets = torch.where(bad_t, torch.full_like(targets, -1), targets).to(torch.int32)
+    return users.contiguous(), targets.contiguous()
+
+
+def _rows(t):
+    return t if t.stride(1) == 1 or t.shape[0] == 0 else t.contiguous()
+
+
+def _rank_launch(ue, ie, users, targets, mrow, mit, rank, score, part, n_splits):
+    """One lgcn_score_rank on prepared device tensors (int32 users / targets / outputs of one
+    length n > 0, part >= n_splits * n int32), on the current stream."""
+    from . import engine
+    lib = engine.load_library()
+    dev = ie.device
+    P = engine._ptr
+    with torch.cuda.device(dev):
+        engine._check(lib.lgcn_score_rank(P(ue), ue.stride(0), P(users), int(users.numel()), P(ie),
+                                          ie.stride(0), int(ie.shape[0]), int(ie.shape[1]), P(mrow),
+                                          P(mit), P(targets), n_splits, P(part), P(score), P(rank),
+                                          engine._stream(dev)), "lgcn_score_rank")
+
+
+def rank_fused(user_emb, item_emb, users, targets, mask_rowptr, mask_items):
+    """(ranks int32 [n], target_scores fp32 [n]) on the tables' HIP device: lgcn_score_rank for
+    batch slot b = (users[b], targets[b]). mask_rowptr / mask_items that are already int32 tensors
+    on the device are passed as they are; numpy arrays are uploaded. A width the kernel does not
+    have is an error (rank_torch takes any)."""
+    from .engine import LgcnError
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    if dev.type != "cuda":
+        raise LgcnError("rank_fused needs tables on a HIP device (rank_torch runs anywhere)")
+    if item_emb.shape[1] not in FUSED_DIMS:
+        raise LgcnError(f"rank_fused: d = {item_emb.shape[1]} not in {FUSED_DIMS}")
+    mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev)
+    mit = _mask_tensor("mask_items", mask_items, dev)
+    if mrow.numel() != user_emb.shape[0] + 1:
+        raise ValueError("rank: mask_rowptr must hold one entry per user row and one more")
+    users, targets = _slots(users, targets, user_emb.shape[0], item_emb.shape[0], dev)
+    n = int(users.numel())
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return rank, score
+    if mit.numel() == 0:
+        mit = torch.zeros(1, dtype=torch.int32, device=dev)
+    from . import engine
+    splits = engine.load_library().lgcn_eval_splits(n, int(item_emb.shape[0]), _device_cus(dev))
+    part = torch.empty(splits * n, dtype=torch.int32, device=dev)
+    _rank_launch(_rows(user_emb), _rows(item_emb), users, targets, mrow, mit, rank, score, part,
+                 splits)
+    return rank, score
+
+
+def rank_torch(user_emb, item_emb, users, targets, mask_rowptr, mask_items, batch_size=1024):
+    """rank_fused's result with torch ops, for any width and device (CPU included): scores by
+    matmul (main.py:420), the user's train items filled with -1e10 (main.py:422-424), then the
+    count of items ahead of the target under the total order. Its scores are matmul's, so on
+    rounded inputs a rank may differ from the kernel's where two scores meet in the last bit."""
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    n_table, n_items = user_emb.shape[0], item_emb.shape[0]
+    mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev).long()
+    mit = _mask_tensor("mask_items", mask_items, dev).long()
+    if mrow.numel() != n_table + 1:
+        raise ValueError("rank: mask_rowptr must hold one entry per user row and one more")
+    users, targets = _slots(users, targets, n_table, n_items, dev)
+    users, targets = users.long(), targets.long()
+    n = int(users.numel())
+    rank = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    score = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    if n == 0 or n_items == 0:
+        return rank, score
+    item = torch.arange(n_items, device=dev)
+    for s in range(0, n, batch_size):
+        u, t = users[s:s + batch_size], targets[s:s + batch_size]
+        scores = torch.matmul(user_emb[u], item_emb.T)
+        lens = mrow[u + 1] - mrow[u]
+        total = int(lens.sum())
+        if total:
+            rr = torch.repeat_interleave(torch.arange(len(u), device=dev), lens)
+            first = torch.cumsum(lens, 0) - lens
+            pos = torch.arange(total, device=dev) - first[rr] + mrow[u][rr]
+            scores[rr, mit[pos]] = -1e10
+        ok = t >= 0
+        tc = t.clamp(min=0)[:, None]
+        ts = scores.gather(1, tc)
+        ahead = (scores > ts) | ((scores == ts) & (item[None, :] < tc))
+        rank[s:s + batch_size] = torch.where(ok, ahead.sum(1), torch.full_like(t, -1)).int()
+        score[s:s + batch_size] = torch.where(ok, ts[:, 0], torch.full_like(ts[:, 0], float("nan")))
+    return rank, score
+
+
+def metrics_from_ranks(ranks, ks=(20,)):
+    """{'recall@k', 'ndcg@k' for k in ks, 'mrr'} from 0-based ranks (a tensor or an array; -1 = no
+    rank, a miss everywhere): the float64 numpy expressions of evaluate(), whose list position of
+    a hit is the rank. Empty input gives NaN, as evaluate() does."""
+    if torch.is_tensor(ranks):
+        ranks = ranks.detach().cpu().numpy()
+    r = np.asarray(ranks).astype(np.int64).reshape(-1)
+    out = {}
+    for k in ks:
+        k = int(k)
+        found = (r >= 0) & (r < k)
+        pos = np.where(found, r, 0)
+        ndcg = np.where(found, 1.0 / np.log2(pos + 2), 0.0)
+        out[f"recall@{k}"] = float(found.mean()) if len(found) else float("nan")
+        out[f"ndcg@{k}"] = float(ndcg.mean()) if len(found) else float("nan")
+    ranked = r >= 0
+    rr = np.where(ranked, 1.0 / (np.where(ranked, r, 0) + 1), 0.0)
+    out["mrr"] = float(rr.mean()) if len(r) else float("nan")
+    return out
+
+
+class Evaluator:
+    """Evaluator(train_users, train_items, num_users, num_items, device)
+
+    Leave-one-out evaluation (main.py:404-439) that stays on the device. Built once: the train
+    mask (mask_csr: per user the sorted, de-duplicated train items) is computed and uploaded here
+    and never again; `from_sampler` takes a BprSampler's resident copy of the same CSR instead.
+
+        ev = Evaluator.from_sampler(sampler)          # or Evaluator(train_u, train_i, U, I, dev)
+        metrics = ev.evaluate(model, adj, val_df, ks=(10, 20, 50))
+
+    Device dispatch, as the sampler's: tables on a HIP device with a width in FUSED_DIMS run
+    lgcn_score_rank (no fallback for them), any other width and a CPU device run rank_torch."""
+
+    def __init__(self, train_users, train_items, num_users, num_items, device):
+        users = np.asarray(train_users, dtype=np.int64)
+        items = np.asarray(train_items, dtype=np.int64)
+        if users.ndim != 1 or users.shape != items.shape:
+            raise ValueError("Evaluator: train_users and train_items must be 1-D and of one length")
+        num_users, num_items = int(num_users), int(num_items)
+        if not (0 <= num_users < 1 << 31 and 0 <= num_items < 1 << 31 and users.size < 1 << 31):
+            raise ValueError("Evaluator: num_users, num_items and the interaction count must be "
+                             "below 2^31")
+        if users.size and (users.min() < 0 or users.max() >= num_users or items.min() < 0
+                           or items.max() >= num_items):
+            raise ValueError("Evaluator: an interaction lies outside [0, num_users) x "
+                             "[0, num_items)")
+        rowptr, it = mask_csr(users, items, num_users)
+        dev = self._device(device)
+        if dev.type == "cuda":
+            from . import engine
+            engine.load_library()  # a missing kernel is an error, here and not at the first call
+        self._init(torch.from_numpy(rowptr).to(dev),
+                   torch.from_numpy(np.ascontiguousarray(it, dtype=np.int32)).to(dev), num_users,
+                   num_items, dev)
+
+    @staticmethod
+    def _device(device):
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:  # tensors report 'cuda:<current>'
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return dev
+
+    def _init(self, rowptr, items, num_users, num_items, dev):
+        if items.numel() == 0:  # a pointer to pass when every list is empty
+            items = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._rowptr, self._items = rowptr, items
+        self.num_users, self.num_items, self.device = num_users, num_items, dev
+
+    @classmethod
+    def from_sampler(cls, sampler):
+        """The evaluator of a BprSampler's train interactions: its pos_rowptr / pos_items are the
+        mask CSR (include/lgcn.h), so they are held, not rebuilt or copied."""
+        self = cls.__new__(cls)
+        rowptr, items = sampler._rowptr, sampler._pos_items
+        if not torch.is_tensor(rowptr):  # a CPU sampler keeps numpy: the same memory as tensors
+            rowptr, items = torch.from_numpy(rowptr), torch.from_numpy(items)
+        self._init(rowptr, items, sampler.num_users, sampler.num_items, cls._device(sampler.device))
+        return self
+
+    def ranks(self, model, adj, eval_users, eval_items, batch_size=8192):
+        """The rank of eval_items[j] for eval_users[j], as one int32 tensor on the device: one
+        propagation under no_grad in model.eval() (left in eval mode, as main.py's evaluate leaves
+        it), then one lgcn_score_rank per batch on views of the device-resident users and targets.
+        No read-back. A pair outside [0, num_users) x [0, num_items) ranks -1."""
+        from .engine import LgcnError
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("Evaluator.ranks: batch_size must be positive")
+        model.eval()
+        with torch.no_grad():
+            ue, ie = model(adj)[:2]
+            _check_tables(ue, ie)
+            if ie.device != self.device:
+                raise LgcnError(f"Evaluator on {self.device}, the model's tables on {ie.device}")
+            if ue.shape[0] != self.num_users or ie.shape[0] != self.num_items:
+                raise LgcnError(f"Evaluator for {self.num_users} x {self.num_items}, the model's "
+                                f"tables are {ue.shape[0]} x {ie.shape[0]}")
+            if not (ie.is_cuda and ie.shape[1] in FUSED_DIMS):
+                return rank_torch(ue, ie, eval_users, eval_items, self._rowptr, self._items,
+                                  min(batch_size, 1024))[0]
+            users, targets = _slots(eval_users, eval_items, self.num_users, self.num_items,
+                                    self.device)
+            n = int(users.numel())
+            rank = torch.empty(n, dtype=torch.int32, device=self.device)
+            if n == 0:
+                return rank
+            from . import engine
+            lib = engine.load_library()
+            score = torch.empty(n, dtype=torch.float32, device=self.device)
+            cus = _device_cus(self.device)
+            sizes = sorted({min(batch_size, n), n % batch_size or min(batch_size, n)})
+            splits = {b: lib.lgcn_eval_splits(b, self.num_items, cus) for b in sizes}
+            part = torch.empty(max(b * s for b, s in splits.items()), dtype=torch.int32,
+                               device=self.device)
+            ue, ie = _rows(ue), _rows(ie)
+            for s in range(0, n, batch_size):
+                e = min(s + batch_size, n)
+                _rank_launch(ue, ie, users[s:e], targets[s:e], self._rowptr, self._items,
+                             rank[s:e], score[s:e], part, splits[e - s])
+        return rank
+
+    def evaluate(self, model, adj, eval_data, ks=(20,)):
+        """metrics_from_ranks of ranks(): eval_data is a (users, items) pair, or a DataFrame (any
+        mapping) with 'user_idx' / 'item_idx', one held-out item per user as
+        dict(zip(user_idx, item_idx)) keeps them (the last one wins). One read-back."""
+        if hasattr(eval_data, "keys") and "user_idx" in eval_data.keys():
+            held = dict(zip(eval_data["user_idx"], eval_data["item_idx"]))
+            users = np.fromiter(held.keys(), dtype=np.int64, count=len(held))
+            items = np.fromiter(held.values(), dtype=np.int64, count=len(held))
+        else:
+            users, items = eval_data
+        return metrics_from_ranks(self.ranks(model, adj, users, items), ks)

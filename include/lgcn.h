@@ -45,8 +45,8 @@ extern "C" {
 
 /* 14 since the sided propagation; the training-step entry points (lgcn_bpr_loss_indexed,
  * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) and the sampler (lgcn_bpr_sample,
- * LGCN_TUNE_SAMPLE_BLOCKS) were added without a bump: purely additive, no existing symbol, struct
- * or constant changed. */
+ * LGCN_TUNE_SAMPLE_BLOCKS) and the rank evaluation (lgcn_score_rank) were added without a bump:
+ * purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -740,6 +740,31 @@ int lgcn_score_topk(const float* user_emb, int64_t ld_u, const int32_t* users, i
                     const int32_t* mask_rowptr, const int32_t* mask_items, int32_t k,
                     int32_t n_splits, float* part_scores, int32_t* part_idx, float* top_scores,
                     int32_t* top_idx, void* stream);
+
+/* Leave-one-out evaluation without a top-k: the rank of one held-out item per batch slot among
+ * all items, under lgcn_score_topk's total order (score descending, item index ascending, the
+ * user's train items at -1e10, a value and not a sentinel). For slot b with u = users[b] and
+ * t = targets[b]:
+ *   score(i)        = the ordered fmaf chain lgcn_score_topk computes for (u, i), replaced by
+ *                     fp32(-1e10) iff i is in mask_items[mask_rowptr[u]:mask_rowptr[u+1]];
+ *   rank[b]         = #{ i in [0, n_items), i != t : score(i) > score(t), or score(i) == score(t)
+ *                     and i < t }: the 0-based place t has in lgcn_score_topk's list whenever it
+ *                     appears there, for any k; Recall@k = (rank < k), NDCG@k = 1/log2(rank + 2);
+ *   target_score[b] = score(t) (-1e10 when t is one of u's train items).
+ * A slot whose t lies outside [0, n_items) gets rank -1 and target_score NaN; nothing of it is
+ * dereferenced. Every score that enters a comparison is bitwise the MFMA tile's value for its
+ * (user, item) pair, and the counts are integers: the result does not depend on n_splits, the
+ * launch geometry, the slot's place in the batch or the run. d in {32, 64, 128, 256}, 16-B
+ * aligned rows, n_splits in [1, 256] (lgcn_eval_splits). part: scratch [n_splits x n_users];
+ * target_score is read back by the later kernels of the call. Allocates nothing, never
+ * synchronises, everything on `stream` (capture-safe). The sizes and the alignment are checked
+ * first; then n_users == 0 returns 0 and touches no pointer; otherwise every pointer must be
+ * non-NULL, except mask_items when every list is empty. */
+int lgcn_score_rank(const float* user_emb, int64_t ld_u, const int32_t* users, int32_t n_users,
+                    const float* item_emb, int64_t ld_i, int32_t n_items, int32_t d,
+                    const int32_t* mask_rowptr, const int32_t* mask_items,
+                    const int32_t* targets, int32_t n_splits, int32_t* part, float* target_score,
+                    int32_t* rank, void* stream);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,11 @@ class LightGCN(nn.Module):
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle)
 
+    def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
+        """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass
+        (evaluate.Evaluator: the held-out item's exact rank per user, one read-back)."""
+        return evaluator.evaluate(self, adj, (eval_users, eval_items), ks)
+
     # -- LightGCN-style accessor (north_star "computer()") --------------------------------------
     def set_graph(self, adj_mat):
         self._graph_adj = adj_mat
