@@ -7,6 +7,11 @@ bias + leaky_relu in its epilogue). The backward is the same arithmetic autograd
 the reference expression, written out with torch ops (training only): g = dF where F > 0, else
 slope * dF; d_id = g · W[:, :d]; dW = gᵀ · [id | content]; db = Σ g. The content table is a
 buffer (no gradient), as in the reference.
+
+The backward reads the branch from the sign of the saved output, which equals the sign of z only
+for slope >= 0 (a negative z times a negative slope is positive). fused_item_embedding therefore
+sends slope < 0 to the torch expression, and FusionPreLayer refuses it. The C entry's forward is
+valid for any slope.
 """
 
 import torch
@@ -21,9 +26,20 @@ def supported(d, c_dim):
     return d in SUPPORTED_D and c_dim in SUPPORTED_C
 
 
+def uses_kernel(device_type, d, c_dim, weight_shape, slope):
+    """Whether fused_item_embedding runs the engine kernel for these arguments: a HIP device, a
+    supported (d, c_dim), the Linear's weight [d x (d + c_dim)] and slope >= 0 (the backward
+    takes its branch from the sign of the output)."""
+    return device_type == "cuda" and supported(d, c_dim) and \
+        tuple(weight_shape) == (d, d + c_dim) and slope >= 0
+
+
 class FusionPreLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, id_w, content, weight, bias, slope):
+        if not slope >= 0:
+            raise engine.LgcnError(f"FusionPreLayer: slope {slope} < 0 (the backward reads the "
+                                   "branch from the output's sign); use the torch expression")
         lib = engine.load_library()
         n, d = id_w.shape
         c_dim = content.shape[1]
@@ -57,9 +73,9 @@ class FusionPreLayer(torch.autograd.Function):
 
 def fused_item_embedding(id_w, content, linear, slope=0.01):
     """leaky_relu(linear(cat([id_w, content], 1))) — the engine kernel on a HIP device for the
-    supported shapes, the reference's torch ops otherwise (CPU tensors, other dims)."""
-    if id_w.device.type == "cuda" and supported(id_w.shape[1], content.shape[1]) and \
-            linear.weight.shape == (id_w.shape[1], id_w.shape[1] + content.shape[1]):
+    supported shapes and slope >= 0, the reference's torch ops otherwise (CPU tensors, other
+    dims, a negative slope)."""
+    if uses_kernel(id_w.device.type, id_w.shape[1], content.shape[1], linear.weight.shape, slope):
         return FusionPreLayer.apply(id_w, content, linear.weight, linear.bias, slope)
     combined = torch.cat([id_w, content], dim=1)
     return torch.nn.functional.leaky_relu(linear(combined), slope)

@@ -715,8 +715,20 @@ int lgcn_bpr_sample(const int32_t* inter_user, const int32_t* inter_item, int64_
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,
  * i.e. F.leaky_relu(nn.Linear(d + c_dim, d)(torch.cat([id, content], 1))) without the
  * concatenation: exact-f32 MFMA GEMM with the bias and activation fused into its epilogue.
- * weight: [d x (d + c_dim)] row-major (nn.Linear.weight); bias: [d] or NULL. d in {64, 128},
- * c_dim in {32, 64, 128}; 16-B aligned rows. */
+ * weight: [d x (d + c_dim)] row-major (nn.Linear.weight), dense; bias: [d] or NULL (NULL = no
+ * bias: the bits of an all-zero bias). d in {64, 128}, c_dim in {32, 64, 128}; id_emb, content
+ * and out: 16-B aligned rows (pointer and leading dim; weight and bias are read by element).
+ * z is an fp32 sum of the d + c_dim products from +0 in a fixed order that does not depend on
+ * where the row sits or on n_items, plus the bias; out = z > 0 ? z : z * slope, for any slope
+ * (the sign of the output equals the sign of z only for slope >= 0: fusion.py's backward reads
+ * it, so its wrapper sends slope < 0 to the torch expression). NaN and infinities follow IEEE
+ * arithmetic (0 * inf is a NaN) and stay within their row.
+ * Writes exactly out[i, 0..d) for i < n_items: never the columns [d, ld_out) of a row, never a
+ * row >= n_items; reads only rows < n_items of id_emb and content.
+ * Checks, in this order: n_items < 0, d or c_dim unsupported, a leading dim below its width
+ * (LGCN_EINVAL); then n_items == 0 returns 0, launches nothing and looks at no pointer (all may
+ * be NULL or misaligned); then id_emb, content, weight or out NULL (LGCN_EINVAL); then id_emb,
+ * content or out not 16-B aligned, or a leading dim not a multiple of 4 (LGCN_EALIGN). */
 int lgcn_fusion_prelayer(const float* id_emb, int64_t ld_id, const float* content, int64_t ld_c,
                          int32_t n_items, int32_t d, int32_t c_dim, const float* weight,
                          const float* bias, float slope, float* out, int64_t ld_out,
