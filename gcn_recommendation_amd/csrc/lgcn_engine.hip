@@ -445,6 +445,24 @@ int scale_rows(const lgcn_rows_t& x, int32_t n_rows, int32_t d, float div, float
     return dispatch_geo(g, f);
 }
 
+struct MeanEmptyF {
+    const int32_t* row_ids; int32_t n; const lgcn_rows_t* e0; int32_t dW; float div;
+    int32_t inv_bits; float* y; int64_t ldy; hipStream_t s;
+    template <typename V, int G, int NV> int operator()() const {
+        return launch_mean_empty_t<V, G, NV>(row_ids, n, *e0, dW, div, inv_bits, y, ldy, s);
+    }
+};
+
+// y[row_ids[i]] = (E0[row_ids[i]] + 0) / div for i < n: the MEAN of rows without a record
+int mean_empty(const int32_t* row_ids, int32_t n, const lgcn_epilogue_t& ep_in, float* y,
+               int64_t ldy, int32_t d, hipStream_t s) {
+    const lgcn_epilogue_t ep = with_pow2(ep_in);
+    const bool vec_ok = rows_aligned(ep.prev0) && al16(y) && (ldy % 4 == 0);
+    const Geo g = pick_geo(d, vec_ok);
+    MeanEmptyF f{row_ids, n, &ep.prev0, g.dW, ep.div, ep.pad, y, ldy, s};
+    return dispatch_geo(g, f);
+}
+
 lgcn_rows_t dense_rows(const float* p, int32_t n, int64_t ld) {
     lgcn_rows_t r;
     r.p0 = r.p1 = r.p2 = p;
@@ -1518,7 +1536,16 @@ struct LayerIO {
 // Segment g of layer k: slots [lo, hi) under plans[2 * g + (k & 1)] on lane L.
 int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
               int32_t lo, int32_t hi, const lgcn_hub_plan_t* plans, int k, int g,
-              const LayerIO& io, int32_t d, const lgcn_sched* sc, const Lane& L, Deps* dp) {
+              const LayerIO& io, int32_t d, const lgcn_sched* sc, const Lane& L, Deps* dp,
+              int32_t empty_tail = 0) {
+    if (empty_tail > 0) {
+        // the segment's last slots hold rows without a record that no record references: the
+        // launches end before them. A STORE leaves them unwritten (nothing gathers them); their
+        // mean needs E0 alone, so it waits for nothing but its lane.
+        hi -= empty_tail;
+        if (io.ep.mode == LGCN_EPI_MEAN)
+            if (int e = mean_empty(row_ids + hi, empty_tail, io.ep, io.y, d, d, L.main)) return e;
+    }
     if (hi <= lo) {  // nothing to run: the deferred parts are "done" here
         if (dp && dp->defer && sc)
             for (int i = 0; i < 2; ++i)
@@ -1568,7 +1595,8 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
 // the parts it waited for read.
 int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
               const lgcn_sides_t& sd, const lgcn_hub_plan_t* plans, int32_t d, int32_t K,
-              const std::function<LayerIO(int)>& layer, const lgcn_sched* sched, hipStream_t s) {
+              const std::function<LayerIO(int)>& layer, const lgcn_sched* sched, hipStream_t s,
+              const int32_t* empty_tail = nullptr) {
     Lane lanes[2];
     bool l1_aux = false;
     if (sched) sched->pool->next = 0;
@@ -1611,7 +1639,7 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
                 dp.late_emu[1] = part[k - 1][1];
             }
             if (int e = seg_layer(rowptr, edges, row_ids, sd.split, n, plans, k, 3, io, d, sched,
-                                  L, &dp))
+                                  L, &dp, empty_tail ? empty_tail[3] : 0))
                 return e;
             if (k < K && sched) {
                 if (int e = record(sched, L.main, &rest[k])) return e;
@@ -1633,7 +1661,7 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
                 Deps dp;
                 if (mean && k >= 2) dp.late[0] = cls[k - 1][c];
                 if (int e = seg_layer(rowptr, edges, row_ids, lo[c], seg_hi(c, n), plans, k, c,
-                                      io, d, sched, L, &dp))
+                                      io, d, sched, L, &dp, empty_tail ? empty_tail[c] : 0))
                     return e;
                 if (sched)
                     if (int e = record(sched, L.main, &cls[k][c])) return e;
@@ -1832,6 +1860,16 @@ int lgcn_propagate_forward_sides(const int32_t* rowptr, const lgcn_edge_t* edges
                                  const lgcn_hub_plan_t* plans, lgcn_rows_t emb, int32_t d,
                                  int32_t K, float* const* layer_bufs_host, float* out,
                                  const lgcn_sched_t* sched, void* stream) {
+    return lgcn_propagate_forward_sides_lean(rowptr, edges, row_ids, sides, plans, nullptr, emb, d,
+                                             K, layer_bufs_host, out, sched, stream);
+}
+
+int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* edges,
+                                      const int32_t* row_ids, const lgcn_sides_t* sides,
+                                      const lgcn_hub_plan_t* plans, const lgcn_lean_t* lean,
+                                      lgcn_rows_t emb, int32_t d, int32_t K,
+                                      float* const* layer_bufs_host, float* out,
+                                      const lgcn_sched_t* sched, void* stream) {
     const int32_t n = sides ? sides->n : -1;
     if (int e = valid_geom(n, d)) return e;
     if (K < 0 || K - 1 > LGCN_MAX_LAYERS || !out) return K < 0 || !out ? LGCN_EINVAL : LGCN_ETOOMANY;
@@ -1858,7 +1896,14 @@ int lgcn_propagate_forward_sides(const int32_t* rowptr, const lgcn_edge_t* edges
         }
         return io;
     };
-    return run_sides(rowptr, edges, row_ids, *sides, plans, d, K, layer, sched, s);
+    if (lean) {  // every tail inside its segment
+        const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
+        for (int g = 0; g < kSegs; ++g)
+            if (lean->empty_tail[g] < 0 || lean->empty_tail[g] > b[g + 1] - b[g])
+                return LGCN_EINVAL;
+    }
+    return run_sides(rowptr, edges, row_ids, *sides, plans, d, K, layer, sched, s,
+                     lean ? lean->empty_tail : nullptr);
 }
 
 int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,

@@ -622,6 +622,32 @@ __global__ __launch_bounds__(kBlock) void k_scale_rows(lgcn_rows_t x, int32_t n_
     }
 }
 
+// The MEAN output of rows no stored record touches (slots [0, n_rows) of row_ids): every E_k,
+// k >= 1, of such a row is +0, so the reference's ((E0 + E1) + ...) / (K+1) is (E0 + 0) / (K+1) —
+// the first add turns a -0 of E0 into +0 and quiets a NaN, the later ones change nothing. Reads
+// E0 alone: no layer buffer holds these rows (lgcn_propagate_forward_sides_lean).
+template <typename V, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_mean_empty(const int32_t* __restrict__ row_ids,
+                                                       int32_t n_rows, lgcn_rows_t e0, int32_t dW,
+                                                       float div, int32_t inv_bits,
+                                                       float* __restrict__ y, int64_t ldy) {
+    using T = VT<V>;
+    constexpr int RPB = kBlock / G;
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t slot = (int64_t)blockIdx.x * RPB + threadIdx.x / G;
+    if (slot >= n_rows) return;
+    const int32_t row = row_ids[slot];
+    const float* xr = seg_row(e0, row);
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const int c = lane + q * G;
+        if (c < dW)
+            store_out<V>(y + (int64_t)row * ldy + c * T::W,
+                         div_exact<V>(T::add(load_stream<V>(xr + c * T::W), T::zero()), div,
+                                      inv_bits));
+    }
+}
+
 // Row-sparsity mask of a block: bit r of mask = row r holds a value != 0 (NaN counts). A block
 // owns 256 rows = 8 mask words (plain stores, no global atomics); one atomicAdd per block
 // accumulates the live-row count.
@@ -834,6 +860,17 @@ int launch_scale_t(const lgcn_rows_t& x, int32_t n_rows, int32_t dW, float div, 
     if (grid == 0) return 0;
     hipLaunchKernelGGL((k_scale_rows<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, x, n_rows,
                        dW, div, y, ldy);
+    return last_err();
+}
+
+template <typename V, int G, int NV>
+int launch_mean_empty_t(const int32_t* row_ids, int32_t n_rows, const lgcn_rows_t& e0, int32_t dW,
+                        float div, int32_t inv_bits, float* y, int64_t ldy, hipStream_t s) {
+    constexpr int RPB = kBlock / G;
+    const int64_t grid = ((int64_t)n_rows + RPB - 1) / RPB;
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL((k_mean_empty<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, row_ids,
+                       n_rows, e0, dW, div, inv_bits, y, ldy);
     return last_err();
 }
 

@@ -147,6 +147,11 @@ class SidesT(ctypes.Structure):
                 ("part_rows", ctypes.c_int32 * 2)]
 
 
+class LeanT(ctypes.Structure):
+    """lgcn_lean_t"""
+    _fields_ = [("empty_tail", ctypes.c_int32 * 4)]
+
+
 class LgcnError(RuntimeError):
     pass
 
@@ -237,6 +242,10 @@ ABI = [
     ("lgcn_propagate_forward_sides", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(SidesT),
                                                     ctypes.POINTER(PlanT), RowsT, _I32, _I32, _P,
                                                     _P, _P, _P]),
+    ("lgcn_propagate_forward_sides_lean", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(SidesT),
+                                                         ctypes.POINTER(PlanT),
+                                                         ctypes.POINTER(LeanT), RowsT, _I32, _I32,
+                                                         _P, _P, _P, _P]),
     ("lgcn_propagate_backward_sides", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(SidesT),
                                                      ctypes.POINTER(PlanT), RowsT, _P, _I32, _I32,
                                                      _P, _P, _P, _P]),
@@ -624,6 +633,7 @@ class Graph:
         self._plans = {}
         self._rowptr_host = None
         self._row_ids_host = None
+        self._lean = None
 
     def rowptr_host(self):
         """Row pointers in storage order (slots when degree-ordered)."""
@@ -687,6 +697,26 @@ class Graph:
                 for a, b in self.segments()]
         return self._plans[key]
 
+    def lean(self):
+        """The LeanPlan of this side-major graph (cached with it: Â is fixed for a training
+        run)."""
+        if self.split is None:
+            raise LgcnError("lean needs a side-ordered graph (graph_from_coo(adj, sides=...))")
+        if self._lean is None:
+            self._lean = lean_plan(self.rowptr, self.edges, self.row_ids, self.split,
+                                   self.segments())
+        return self._lean
+
+    @property
+    def n_empty(self):
+        """Rows in the `empty` mask of lean()."""
+        return self.lean().n_empty
+
+    @property
+    def n_derived(self):
+        """Rows in the `derived` mask of lean()."""
+        return self.lean().n_derived
+
     def degrees(self):
         """Degree of every row, indexed by row id."""
         deg = np.diff(self.rowptr_host().astype(np.int64))
@@ -696,6 +726,78 @@ class Graph:
         out = np.empty_like(deg)
         out[ids] = deg
         return out
+
+
+def _bitmask(flags):
+    """Row flags (bool [n]) as lgcn_rows_nonzero's mask: bit r & 31 of int32 word r >> 5."""
+    n = flags.numel()
+    pad = torch.zeros(((n + 31) // 32) * 32, dtype=torch.int64, device=flags.device)
+    pad[:n] = flags
+    w = (pad.view(-1, 32) << torch.arange(32, dtype=torch.int64, device=flags.device)).sum(1)
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
+
+
+class LeanPlan:
+    """Rows of a side-major CSR whose intermediate layers the forward's result does not need
+    (DESIGN §4g). Bitmasks by row id, lgcn_rows_nonzero's format:
+      empty:   the row holds no stored record and no stored record names it as its column, so
+               every layer of it but E0 is +0 and nothing gathers it;
+      derived: a side-0 row with exactly one stored record (p, w), every stored record naming it
+               as its column lying in row p with w's value bits — its layer-k row is
+               fma(w, E_{k-1}[p], +0), which row p can form itself. No kernel uses this mask yet.
+    empty_tail[g]: the trailing slots of segment g (Graph.segments()) whose rows are all `empty`
+    — what lgcn_propagate_forward_sides_lean takes."""
+
+    def __init__(self, empty, derived, n_empty, n_derived, empty_tail):
+        self.empty, self.derived = empty, derived
+        self.n_empty, self.n_derived = n_empty, n_derived
+        self.empty_tail = tuple(empty_tail)
+
+    def struct(self):
+        st = LeanT()
+        for g, t in enumerate(self.empty_tail):
+            st.empty_tail[g] = t
+        return st
+
+
+def lean_plan(rowptr, edges, row_ids, split, segments):
+    """LeanPlan of a CSR in side-major slots (slot s = row row_ids[s], side 0 = slots
+    [0, split)); rowptr / edges / row_ids as Graph holds them, on any device (torch ops only, so
+    it runs on CPU tensors too). Duplicate records count one each, value bits compare exactly."""
+    dev = rowptr.device
+    n = rowptr.numel() - 1
+    nnz = int(rowptr[-1])
+    ids = row_ids.long()
+    deg_slot = (rowptr[1:] - rowptr[:-1]).long()
+    rec = edges[:nnz]
+    col = rec & 0xffffffff
+    bits = rec >> 32  # (arithmetic shift: equal bits <-> equal values of it)
+    row = torch.repeat_interleave(ids, deg_slot)  # the row of every record
+    deg = torch.zeros(n, dtype=torch.int64, device=dev)
+    deg[ids] = deg_slot
+    named = torch.zeros(n, dtype=torch.bool, device=dev)
+    named[col] = True
+    empty = (deg == 0) & ~named
+    # the one record (p, w) of every single-record row, by row id
+    one_slot = deg_slot == 1
+    first = rec[rowptr[:-1].long()[one_slot]]
+    p = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    w = torch.zeros(n, dtype=torch.int64, device=dev)
+    p[ids[one_slot]] = first & 0xffffffff
+    w[ids[one_slot]] = first >> 32
+    side0 = torch.zeros(n, dtype=torch.bool, device=dev)
+    side0[ids[:split]] = True
+    # a record (row a, column r, bits b) agrees with r's own record when a == p[r] and b == w[r]
+    other = torch.zeros(n, dtype=torch.bool, device=dev)
+    other[col[(row != p[col]) | (bits != w[col])]] = True
+    derived = (deg == 1) & side0 & ~other
+    tails = []
+    for a, b in segments:
+        e = empty[ids[a:b]]
+        live = torch.nonzero(~e)
+        tails.append(int(b - a - (int(live[-1]) + 1 if live.numel() else 0)))
+    return LeanPlan(_bitmask(empty), _bitmask(derived), int(empty.sum()), int(derived.sum()),
+                    tails)
 
 
 def slot_key_enabled(g):
@@ -1295,8 +1397,15 @@ def _collect_sides(ev, K, graph):
                            for k in range(1, K + 1) for g in segs})
 
 
+def alloc_layers(n, d, count, device):
+    """The forward's intermediate layer buffers (a test replaces this to see which rows a lean
+    forward leaves unwritten)."""
+    return [torch.empty((n, d), dtype=torch.float32, device=device) for _ in range(count)]
+
+
 def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
-                      return_layers=False, hub_mode=None, emu_min=None, kernel_events=None):
+                      return_layers=False, hub_mode=None, emu_min=None, kernel_events=None,
+                      lean=None):
     """final = mean(E0, Â E0, ..., Â^K E0) with E0 = cat(segments) (never materialised).
 
     layer_events: optional list of (start, end) torch.cuda.Event pairs recorded on the current
@@ -1304,6 +1413,11 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
     each layer's layer-kernel launch alone (spmm_layer) — bench.py's live timing. A side-ordered
     graph runs the bipartite two-lane schedule (lgcn_propagate_forward_sides) unless per-layer
     events are asked for.
+    lean: the sided forward without the rows its result does not need (LeanPlan: the layer
+    buffers' `empty` rows stay unwritten; same final bits, exact and chunk plans alike). None:
+    on when the layers are private to the call (no return_layers); True with return_layers hands
+    back layers whose skipped rows hold whatever the buffers held. No effect on the one-operator
+    schedule.
     """
     if hub_threshold is None:
         hub_threshold = hub_threshold_from_env()
@@ -1323,8 +1437,11 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
         if K == 0:
             _check(lib.lgcn_scale_rows(e0, n, d, 1.0, _ptr(out), d, stream), "lgcn_scale_rows")
             return (out, []) if return_layers else out
-        layers = [torch.empty((n, d), dtype=torch.float32, device=dev) for _ in range(K - 1)]
+        layers = alloc_layers(n, d, K - 1, dev)
         if use_sides(graph, layer_events, kernel_events):
+            if lean is None:
+                lean = not return_layers
+            lp = graph.lean().struct() if lean else None
             plans, _ = _side_plans(graph, d, hub_threshold, hub_mode, emu_min,
                                    _aligned16(segments))
             sc = sched_for(dev)
@@ -1332,10 +1449,12 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
             bufs = (ctypes.c_void_p * max(K - 1, 1))(*[t.data_ptr() for t in layers])
             sides = graph.sides_struct()
             try:
-                _check(lib.lgcn_propagate_forward_sides(
+                _check(lib.lgcn_propagate_forward_sides_lean(
                     _ptr(graph.rowptr), _ptr(graph.edges), _ptr(graph.row_ids),
-                    ctypes.byref(sides), plans, e0, d, K, bufs, _ptr(out),
-                    sc.handle if sc is not None else None, stream), "lgcn_propagate_forward_sides")
+                    ctypes.byref(sides), plans, ctypes.byref(lp) if lp is not None else None,
+                    e0, d, K, bufs, _ptr(out),
+                    sc.handle if sc is not None else None, stream),
+                    "lgcn_propagate_forward_sides_lean")
             finally:
                 ev.clear()
             _note_schedule(sc, graph)

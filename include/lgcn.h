@@ -610,6 +610,23 @@ int lgcn_propagate_forward_sides(const int32_t* rowptr, const lgcn_edge_t* edges
                                  const lgcn_hub_plan_t* plans, lgcn_rows_t emb, int32_t d,
                                  int32_t K, float* const* layer_bufs_host, float* out,
                                  const lgcn_sched_t* sched, void* stream);
+/* lgcn_propagate_forward_sides without the rows the result does not need. empty_tail[g]: the
+ * last empty_tail[g] slots of segment g hold rows with no stored record that no stored record
+ * names as its column (slots are degree-ordered, so such rows end their segment). Every layer of
+ * such a row but E0 is +0 and nothing gathers it: the STORE layers' launches end before these
+ * slots and leave their rows of layer_bufs_host UNWRITTEN, and the final mean writes
+ * (E0 + 0) / (K+1) for them from E0 alone — the reference's bits. `out` is bitwise that of
+ * lgcn_propagate_forward_sides; the layer buffers are private to the call (a caller that reads
+ * them passes lean = NULL, which is lgcn_propagate_forward_sides itself). */
+typedef struct {
+    int32_t empty_tail[4];
+} lgcn_lean_t;
+int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* edges,
+                                      const int32_t* row_ids, const lgcn_sides_t* sides,
+                                      const lgcn_hub_plan_t* plans, const lgcn_lean_t* lean,
+                                      lgcn_rows_t emb, int32_t d, int32_t K,
+                                      float* const* layer_bufs_host, float* out,
+                                      const lgcn_sched_t* sched, void* stream);
 int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,
                                   const int32_t* row_ids, const lgcn_sides_t* sides,
                                   const lgcn_hub_plan_t* plans, lgcn_rows_t grad_out,
