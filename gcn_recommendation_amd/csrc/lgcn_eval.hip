@@ -16,9 +16,19 @@
 //    deterministic regardless of LDS arrival order;
 //  * k_topk_merge: per user, the splits' K-th scores bound the global K-th from below, so only
 //    candidates >= max_s kth_s are ranked.
+//
+// lgcn_score_rank (further down) ranks one held-out item per user under the same total order. Both
+// entry points stand on the same pieces, each written once: load_row_half (guarded row load),
+// score_tile (the one MFMA chain: every score either entry point compares comes from it), c_row
+// (which user row a C register holds), and on the host eval_args, eval_split_len, user_tiles and
+// with_width. The double-buffered loop over an item split stays written out in k_score_topk and
+// in k_rank_count: as one template over a consumer callable, the consumer is optimised on its own
+// before it is inlined, and k_rank_count's comparisons then compile to other code.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "lgcn.h"
 
@@ -92,6 +102,38 @@ __device__ void compact_user(WaveState& st, int u, int K, int lane) {
     __builtin_amdgcn_wave_barrier();
 }
 
+// Half a row (this lane half's D/2 features, starting at p) as float4s; zeros when !ok (p is then
+// any valid address: nothing is read).
+template <int D>
+__device__ __forceinline__ void load_row_half(const float* __restrict__ p, bool ok,
+                                              float4 (&v)[D / 8]) {
+#pragma unroll
+    for (int q = 0; q < D / 8; ++q)
+        v[q] = ok ? *reinterpret_cast<const float4*>(p + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// C[user row][item col] = the ordered fmaf chain over the features (feature order 0,32,1,33,… at
+// d = 64). A score is a function of its (user row, item row) pair alone, wherever the pair sits
+// in a tile.
+template <int D>
+__device__ __forceinline__ f32x16 score_tile(const float4 (&a)[D / 8], const float4 (&b)[D / 8]) {
+    f32x16 acc = {};
+#pragma unroll
+    for (int q = 0; q < D / 8; ++q) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// Register r of the C tile in lane half h holds user row c_row(r, h) (of column lane & 31);
+// row = c_row(c_reg(row), c_half(row)).
+__device__ __forceinline__ int c_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+__device__ __forceinline__ int c_reg(int row) { return (row & 3) + 4 * (row >> 3); }
+__device__ __forceinline__ int c_half(int row) { return (row >> 2) & 1; }
+
 template <int D>
 __global__ __launch_bounds__(kWaves * 64) void k_score_topk(
     const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
@@ -115,16 +157,10 @@ __global__ __launch_bounds__(kWaves * 64) void k_score_topk(
         st.thr[lane] = -INFINITY;
     }
     // A operand: user (ub + col), features [h*DH, h*DH + DH)
-    float a[DH];
+    float4 a[D / 8];
     {
         const bool ok = ub + col < n_users;
-        const float* ur = uemb + (ok ? (int64_t)users[ub + col] * ld_u : 0) + h * DH;
-#pragma unroll
-        for (int q = 0; q < DH / 4; ++q) {
-            const float4 v = ok ? *reinterpret_cast<const float4*>(ur + 4 * q)
-                                : make_float4(0.f, 0.f, 0.f, 0.f);
-            a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-        }
+        load_row_half<D>(uemb + (ok ? (int64_t)users[ub + col] * ld_u : 0) + h * DH, ok, a);
     }
     if (lane < kUsersPerWave) {
         const bool ok = ub + lane < n_users;
@@ -135,37 +171,24 @@ __global__ __launch_bounds__(kWaves * 64) void k_score_topk(
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(kLgkm0);
     __builtin_amdgcn_wave_barrier();
-    // rows of the C/D tile this lane holds: user (ub + row(r)), row(r) = (r&3)+8(r>>2)+4h.
     // The B operand (32 items x this lane's feature half) is double-buffered: the next tile's
     // loads are in flight during the current tile's MFMA chain.
-    float4 bcur[DH / 4], bnxt[DH / 4];
-    auto load_tile = [&](int32_t t0, float4 (&b)[DH / 4]) {
+    float4 bcur[D / 8], bnxt[D / 8];
+    auto load_tile = [&](int32_t t0, float4 (&b)[D / 8]) {
         const int32_t item = t0 + col;
         const bool iok = item < it1;
-        const float* ir = iemb + (iok ? (int64_t)item * ld_i : 0) + h * DH;
-#pragma unroll
-        for (int q = 0; q < DH / 4; ++q)
-            b[q] = iok ? *reinterpret_cast<const float4*>(ir + 4 * q)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        load_row_half<D>(iemb + (iok ? (int64_t)item * ld_i : 0) + h * DH, iok, b);
     };
     if (it0 < it1) load_tile(it0, bcur);
-
     for (int32_t t0 = it0; t0 < it1; t0 += 32) {
         if (t0 + 32 < it1) load_tile(t0 + 32, bnxt);
         const int32_t item = t0 + col;
         const bool iok = item < it1;
-        f32x16 acc = {};
-#pragma unroll
-        for (int q = 0; q < DH / 4; ++q) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q], bcur[q].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 1], bcur[q].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 2], bcur[q].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 3], bcur[q].w, acc, 0, 0, 0);
-        }
+        const f32x16 acc = score_tile<D>(a, bcur);
         bool any = false;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int row = c_row(r, h);
             float sc = acc[r];
             const float thr = st.thr[row];
             if (iok && sc > thr) {
@@ -194,7 +217,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_score_topk(
             }
         }
 #pragma unroll
-        for (int q = 0; q < DH / 4; ++q) bcur[q] = bnxt[q];
+        for (int q = 0; q < D / 8; ++q) bcur[q] = bnxt[q];
     }
     // final: every buffer to its K best in rank order, written to this split's partial list
     for (int u = 0; u < kUsersPerWave; ++u) {
@@ -260,9 +283,8 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ par
 
 // ---------------------------------------------------------------------------------------------
 // lgcn_score_rank: the rank of one held-out item per user under the same total order, with no
-// top-K selection. Every score that enters a comparison comes from score_tile below: the MFMA
-// chain of k_score_topk's main loop (a score is a function of its (user row, item row) pair
-// alone, wherever the pair sits in a tile), so one score table explains every rank.
+// top-K selection. Every score that enters a comparison comes from score_tile, as k_score_topk's
+// do, so one score table explains every rank and every list.
 //  1. k_rank_target: per 32 slots a gathered tile (column c = the target of slot c); its diagonal
 //     is score(slot, target). A train item as target scores -1e10. -> target_score
 //  2. k_rank_count: k_score_topk's tile loop without WaveState: per (lane, C-row) an integer
@@ -270,28 +292,6 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ par
 //  3. k_rank_finish: one wave per slot sums the parts and corrects them for the user's train
 //     items (32 per gathered tile): minus what the raw score counted, plus what -1e10 counts.
 // ---------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void load_row_half(const float* __restrict__ p, bool ok,
-                                              float4 (&v)[D / 8]) {
-#pragma unroll
-    for (int q = 0; q < D / 8; ++q)
-        v[q] = ok ? *reinterpret_cast<const float4*>(p + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// C[user row][item col] = the ordered fmaf chain over the features, as in k_score_topk.
-template <int D>
-__device__ __forceinline__ f32x16 score_tile(const float4 (&a)[D / 8], const float4 (&b)[D / 8]) {
-    f32x16 acc = {};
-#pragma unroll
-    for (int q = 0; q < D / 8; ++q) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
 template <int D>
 __global__ __launch_bounds__(kWaves * 64) void k_rank_target(
     const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
@@ -312,12 +312,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_rank_target(
     load_row_half<D>(uemb + (int64_t)u * ld_u + h * DH, ok, a);
     load_row_half<D>(iemb + (tok ? (int64_t)t * ld_i : 0) + h * DH, tok, b);
     const f32x16 acc = score_tile<D>(a, b);
-    // the diagonal: row col of column col is register (col&3) + 4(col>>3) of half (col>>2)&1
-    const int rd = (col & 3) + 4 * (col >> 3);
+    // the diagonal: row col of column col
+    const int rd = c_reg(col);
     float sc = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc = r == rd ? acc[r] : sc;
-    if (ok && h == ((col >> 2) & 1)) {
+    if (ok && h == c_half(col)) {
         if (!tok) sc = __builtin_nanf("");
         else if (in_sorted(mitems, mrow[u], mrow[u + 1], t)) sc = kMasked;
         target_score[slot] = sc;
@@ -366,9 +366,9 @@ __global__ __launch_bounds__(kWaves * 64, D <= 64 ? 3 : 1) void k_rank_count(
         const bool iok = item < it1;
         const f32x16 acc = score_tile<D>(a, bcur);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 ts = *reinterpret_cast<const float4*>(&s_ts[wave][8 * g + 4 * h]);
-            const int4 tg = *reinterpret_cast<const int4*>(&s_tg[wave][8 * g + 4 * h]);
+        for (int g = 0; g < 4; ++g) {  // rows c_row(4g .. 4g+3, h) are four neighbours in LDS
+            const float4 ts = *reinterpret_cast<const float4*>(&s_ts[wave][c_row(4 * g, h)]);
+            const int4 tg = *reinterpret_cast<const int4*>(&s_tg[wave][c_row(4 * g, h)]);
             cnt[4 * g] += (iok && item != tg.x && better(acc[4 * g], item, ts.x, tg.x)) ? 1 : 0;
             cnt[4 * g + 1] +=
                 (iok && item != tg.y && better(acc[4 * g + 1], item, ts.y, tg.y)) ? 1 : 0;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kWaves * 64, D <= 64 ? 3 : 1) void k_rank_count(
         int c = cnt[r];
 #pragma unroll
         for (int off = 16; off > 0; off >>= 1) c += __shfl_xor(c, off);
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = c_row(r, h);
         if (col == 0 && ub + row < n_users) part[(int64_t)split * n_users + ub + row] = c;
     }
 }
@@ -432,6 +432,39 @@ __global__ __launch_bounds__(64) void k_rank_finish(
     if (lane == 0) rank[slot] = c;
 }
 
+// ---- host side ----
+constexpr int64_t user_tiles(int64_t n_users) {  // blocks of kWaves x 32 user slots
+    return (n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
+}
+
+// Items per split: ceil(n_items / n_splits) rounded up to whole 32-item tiles, never zero.
+int32_t eval_split_len(int32_t n_items, int32_t n_splits) {
+    const int32_t len = (int32_t)(((int64_t)n_items + n_splits - 1) / n_splits);
+    return len == 0 ? 32 : ((len + 31) / 32) * 32;
+}
+
+// What both entry points ask of their common arguments.
+int eval_args(const float* user_emb, int64_t ld_u, int32_t n_users, const float* item_emb,
+              int64_t ld_i, int32_t n_items, int32_t d, int32_t n_splits) {
+    if (n_users < 0 || n_items < 0 || n_splits < 1 || n_splits > 256) return LGCN_EINVAL;
+    if (d != 32 && d != 64 && d != 128 && d != 256) return LGCN_EINVAL;
+    if (ld_u % 4 || ld_i % 4 || (reinterpret_cast<uintptr_t>(user_emb) & 15) ||
+        (reinterpret_cast<uintptr_t>(item_emb) & 15))
+        return LGCN_EALIGN;
+    return 0;
+}
+
+// f(std::integral_constant<int, D>{}) for the width d (one eval_args accepted).
+template <class F>
+hipError_t with_width(int32_t d, F&& f) {
+    switch (d) {
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return f(std::integral_constant<int, 256>{});
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -439,7 +472,7 @@ extern "C" {
 int lgcn_eval_splits(int32_t n_users, int32_t n_items, int32_t n_cu) {
     // enough (user tile x split) blocks for ~2 per CU, splits of >= 2048 items, <= 256 splits
     // (no users count as one tile: the answer never grows with n_users)
-    int64_t tiles = ((int64_t)n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
+    int64_t tiles = user_tiles(n_users);
     if (tiles < 1) tiles = 1;
     int64_t s = (2LL * (n_cu > 0 ? n_cu : 256) + tiles - 1) / tiles;
     const int64_t max_by_len = ((int64_t)n_items + 2047) / 2048;
@@ -454,43 +487,28 @@ int lgcn_score_topk(const float* user_emb, int64_t ld_u, const int32_t* users, i
                     const int32_t* mask_rowptr, const int32_t* mask_items, int32_t k,
                     int32_t n_splits, float* part_scores, int32_t* part_idx, float* top_scores,
                     int32_t* top_idx, void* stream) {
-    if (n_users < 0 || n_items < 0 || k < 1 || k > kCompact || n_splits < 1 || n_splits > 256)
-        return LGCN_EINVAL;
-    if (d != 32 && d != 64 && d != 128 && d != 256) return LGCN_EINVAL;
-    if (ld_u % 4 || ld_i % 4 || (reinterpret_cast<uintptr_t>(user_emb) & 15) ||
-        (reinterpret_cast<uintptr_t>(item_emb) & 15))
-        return LGCN_EALIGN;
+    if (k < 1 || k > kCompact) return LGCN_EINVAL;
+    if (const int rc = eval_args(user_emb, ld_u, n_users, item_emb, ld_i, n_items, d, n_splits))
+        return rc;
     if (n_users == 0) return 0;
     if (!user_emb || !users || !item_emb || !mask_rowptr || !part_scores || !part_idx ||
         !top_scores || !top_idx)
         return LGCN_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int32_t split_len = (int32_t)(((int64_t)n_items + n_splits - 1) / n_splits);
-    split_len = ((split_len + 31) / 32) * 32;
-    if (split_len == 0) split_len = 32;
-    const dim3 grid((n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave), n_splits);
+    const int32_t split_len = eval_split_len(n_items, n_splits);
+    const dim3 grid(user_tiles(n_users), n_splits);
     const size_t lds = sizeof(WaveState) * kWaves;
-    const void* fn = d == 32    ? reinterpret_cast<const void*>(k_score_topk<32>)
-                     : d == 64  ? reinterpret_cast<const void*>(k_score_topk<64>)
-                     : d == 128 ? reinterpret_cast<const void*>(k_score_topk<128>)
-                                : reinterpret_cast<const void*>(k_score_topk<256>);
-    {
+    hipError_t e = with_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
         const hipError_t ea =
-            hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-    }
-#define LGCN_SCORE_LAUNCH(D_)                                                                   \
-    hipLaunchKernelGGL(k_score_topk<D_>, grid, dim3(kWaves * 64), lds, s, user_emb, ld_u, users, \
-                       n_users, item_emb, ld_i, n_items, split_len, mask_rowptr, mask_items, k,  \
-                       part_scores, part_idx)
-    switch (d) {
-        case 32: LGCN_SCORE_LAUNCH(32); break;
-        case 64: LGCN_SCORE_LAUNCH(64); break;
-        case 128: LGCN_SCORE_LAUNCH(128); break;
-        default: LGCN_SCORE_LAUNCH(256); break;
-    }
-#undef LGCN_SCORE_LAUNCH
-    hipError_t e = hipGetLastError();
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_topk<D>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (ea != hipSuccess) return ea;
+        hipLaunchKernelGGL(k_score_topk<D>, grid, dim3(kWaves * 64), lds, s, user_emb, ld_u, users,
+                           n_users, item_emb, ld_i, n_items, split_len, mask_rowptr, mask_items, k,
+                           part_scores, part_idx);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return (int)e;
     const size_t mlds = (size_t)n_splits * k * 8;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_users), dim3(64), mlds, s, part_scores, part_idx,
@@ -504,43 +522,31 @@ int lgcn_score_rank(const float* user_emb, int64_t ld_u, const int32_t* users, i
                     const int32_t* mask_rowptr, const int32_t* mask_items,
                     const int32_t* targets, int32_t n_splits, int32_t* part, float* target_score,
                     int32_t* rank, void* stream) {
-    if (n_users < 0 || n_items < 0 || n_splits < 1 || n_splits > 256) return LGCN_EINVAL;
-    if (d != 32 && d != 64 && d != 128 && d != 256) return LGCN_EINVAL;
-    if (ld_u % 4 || ld_i % 4 || (reinterpret_cast<uintptr_t>(user_emb) & 15) ||
-        (reinterpret_cast<uintptr_t>(item_emb) & 15))
-        return LGCN_EALIGN;
+    if (const int rc = eval_args(user_emb, ld_u, n_users, item_emb, ld_i, n_items, d, n_splits))
+        return rc;
     if (n_users == 0) return 0;
     if (!user_emb || !users || !item_emb || !mask_rowptr || !targets || !part || !target_score ||
         !rank)
         return LGCN_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int32_t split_len = (int32_t)(((int64_t)n_items + n_splits - 1) / n_splits);
-    split_len = ((split_len + 31) / 32) * 32;
-    if (split_len == 0) split_len = 32;
-    const int32_t tiles = (n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
-    hipError_t e = hipSuccess;
-#define LGCN_RANK_LAUNCH(D_)                                                                      \
-    do {                                                                                          \
-        hipLaunchKernelGGL(k_rank_target<D_>, dim3(tiles), dim3(kWaves * 64), 0, s, user_emb,     \
-                           ld_u, users, n_users, item_emb, ld_i, n_items, mask_rowptr,            \
-                           mask_items, targets, target_score);                                    \
-        if ((e = hipGetLastError()) != hipSuccess) break;                                         \
-        hipLaunchKernelGGL(k_rank_count<D_>, dim3(tiles, n_splits), dim3(kWaves * 64), 0, s,      \
-                           user_emb, ld_u, users, n_users, item_emb, ld_i, n_items, split_len,    \
-                           targets, target_score, part);                                          \
-        if ((e = hipGetLastError()) != hipSuccess) break;                                         \
-        hipLaunchKernelGGL(k_rank_finish<D_>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u,      \
-                           users, n_users, item_emb, ld_i, n_items, mask_rowptr, mask_items,      \
-                           targets, target_score, part, n_splits, rank);                          \
-        e = hipGetLastError();                                                                    \
-    } while (0)
-    switch (d) {
-        case 32: LGCN_RANK_LAUNCH(32); break;
-        case 64: LGCN_RANK_LAUNCH(64); break;
-        case 128: LGCN_RANK_LAUNCH(128); break;
-        default: LGCN_RANK_LAUNCH(256); break;
-    }
-#undef LGCN_RANK_LAUNCH
+    const int32_t split_len = eval_split_len(n_items, n_splits);
+    const int32_t tiles = user_tiles(n_users);
+    const hipError_t e = with_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        hipLaunchKernelGGL(k_rank_target<D>, dim3(tiles), dim3(kWaves * 64), 0, s, user_emb, ld_u,
+                           users, n_users, item_emb, ld_i, n_items, mask_rowptr, mask_items,
+                           targets, target_score);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rank_count<D>, dim3(tiles, n_splits), dim3(kWaves * 64), 0, s,
+                           user_emb, ld_u, users, n_users, item_emb, ld_i, n_items, split_len,
+                           targets, target_score, part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rank_finish<D>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u, users,
+                           n_users, item_emb, ld_i, n_items, mask_rowptr, mask_items, targets,
+                           target_score, part, n_splits, rank);
+        return hipGetLastError();
+    });
     return e == hipSuccess ? 0 : (int)e;
 }
 

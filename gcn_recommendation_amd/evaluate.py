@@ -5,8 +5,12 @@ masked to -1e10 (main.py:422-424), topk(K) (main.py:426), hit -> recall 1, NDCG 
 (main.py:430-438). The training items come straight from the engine's CSR (a user's row holds its
 items at column offset U), so no Python loop over users is needed.
 """
+import ctypes
+
 import numpy as np
 import torch
+
+from . import engine
 
 
 def recall_ndcg(user_emb, item_emb, users, heldout_items, train_rowptr, train_cols, U, k=20,
@@ -60,11 +64,16 @@ def mask_csr(users, items, n_users):
     return rowptr, it.astype(np.int32)
 
 
+def _items_to_pass(mask_items):
+    """mask_items, or one int32 zero when every list is empty: the kernels want a pointer."""
+    if mask_items.numel():
+        return mask_items
+    return torch.zeros(1, dtype=torch.int32, device=mask_items.device)
+
+
 def topk_fused(user_emb, item_emb, users, mask_rowptr, mask_items, k=20):
     """Top-k items per user (scores, indices) with the train items masked to -1e10.
     user_emb [U x d], item_emb [I x d] fp32 on the HIP device; users: int32/int64 ids."""
-    import ctypes
-    from . import engine
     lib = engine.load_library()
     dev = item_emb.device
     d = item_emb.shape[1]
@@ -72,12 +81,8 @@ def topk_fused(user_emb, item_emb, users, mask_rowptr, mask_items, k=20):
     n = int(users.numel())
     ue, ie = user_emb.contiguous(), item_emb.contiguous()
     mrow = torch.as_tensor(mask_rowptr, device=dev).to(torch.int32).contiguous()
-    mit = torch.as_tensor(mask_items, device=dev).to(torch.int32).contiguous()
-    if mit.numel() == 0:
-        mit = torch.zeros(1, dtype=torch.int32, device=dev)
-    n_cu = ctypes.c_int32(0)
-    engine._check(lib.lgcn_device_info(dev.index or 0, ctypes.byref(n_cu), None), "device_info")
-    splits = lib.lgcn_eval_splits(n, int(ie.shape[0]), n_cu.value)
+    mit = _items_to_pass(torch.as_tensor(mask_items, device=dev).to(torch.int32).contiguous())
+    splits = lib.lgcn_eval_splits(n, int(ie.shape[0]), _device_cus(dev))
     part_s = torch.empty((splits, max(n, 1), k), dtype=torch.float32, device=dev)
     part_i = torch.empty((splits, max(n, 1), k), dtype=torch.int32, device=dev)
     top_s = torch.empty((max(n, 1), k), dtype=torch.float32, device=dev)
@@ -156,8 +161,6 @@ _n_cu = {}
 
 
 def _device_cus(dev):
-    import ctypes
-    from . import engine
     idx = dev.index or 0
     if idx not in _n_cu:
         n_cu = ctypes.c_int32(0)
@@ -168,27 +171,25 @@ def _device_cus(dev):
 
 
 def _check_tables(user_emb, item_emb):
-    from .engine import LgcnError
     for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
         if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32:
-            raise LgcnError(f"rank: {name} must be a 2-D float32 tensor")
+            raise engine.LgcnError(f"rank: {name} must be a 2-D float32 tensor")
     if user_emb.device != item_emb.device or user_emb.shape[1] != item_emb.shape[1]:
-        raise LgcnError("rank: user_emb and item_emb must share a device and a width")
+        raise engine.LgcnError("rank: user_emb and item_emb must share a device and a width")
 
 
 def _index_tensor(name, a, dev):
     """users / targets as a 1-D integer tensor on dev: a tensor must already be there (nothing is
     moved silently), anything else is uploaded once."""
-    from .engine import LgcnError
     if torch.is_tensor(a):
         if a.device != dev:
-            raise LgcnError(f"rank: {name} on {a.device}, tables on {dev}")
+            raise engine.LgcnError(f"rank: {name} on {a.device}, tables on {dev}")
         if a.dtype not in (torch.int32, torch.int64):
-            raise LgcnError(f"rank: {name} must be int32 or int64, not {a.dtype}")
+            raise engine.LgcnError(f"rank: {name} must be int32 or int64, not {a.dtype}")
     else:
         a = np.asarray(a)
         if a.size and a.dtype.kind not in "iu":
-            raise LgcnError(f"rank: {name} must be integers, not {a.dtype}")
+            raise engine.LgcnError(f"rank: {name} must be integers, not {a.dtype}")
         a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
     if a.dim() != 1:
         raise ValueError(f"rank: {name} must be 1-D")
@@ -198,10 +199,9 @@ def _index_tensor(name, a, dev):
 def _mask_tensor(name, a, dev):
     """A mask CSR array as a contiguous int32 tensor on dev: a device tensor is used as it is (no
     upload, no copy), numpy is uploaded."""
-    from .engine import LgcnError
     if torch.is_tensor(a):
         if a.device != dev or a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
-            raise LgcnError(f"rank: {name} must be a contiguous 1-D int32 tensor on {dev}")
+            raise engine.LgcnError(f"rank: {name} must be a contiguous 1-D int32 tensor on {dev}")
         return a
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
 
@@ -228,7 +228,6 @@ def _rows(t):
 def _rank_launch(ue, ie, users, targets, mrow, mit, rank, score, part, n_splits):
     """One lgcn_score_rank on prepared device tensors (int32 users / targets / outputs of one
     length n > 0, part >= n_splits * n int32), on the current stream."""
-    from . import engine
     lib = engine.load_library()
     dev = ie.device
     P = engine._ptr
@@ -244,13 +243,12 @@ def rank_fused(user_emb, item_emb, users, targets, mask_rowptr, mask_items):
     batch slot b = (users[b], targets[b]). mask_rowptr / mask_items that are already int32 tensors
     on the device are passed as they are; numpy arrays are uploaded. A width the kernel does not
     have is an error (rank_torch takes any)."""
-    from .engine import LgcnError
     _check_tables(user_emb, item_emb)
     dev = item_emb.device
     if dev.type != "cuda":
-        raise LgcnError("rank_fused needs tables on a HIP device (rank_torch runs anywhere)")
+        raise engine.LgcnError("rank_fused needs tables on a HIP device (rank_torch runs anywhere)")
     if item_emb.shape[1] not in FUSED_DIMS:
-        raise LgcnError(f"rank_fused: d = {item_emb.shape[1]} not in {FUSED_DIMS}")
+        raise engine.LgcnError(f"rank_fused: d = {item_emb.shape[1]} not in {FUSED_DIMS}")
     mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev)
     mit = _mask_tensor("mask_items", mask_items, dev)
     if mrow.numel() != user_emb.shape[0] + 1:
@@ -261,13 +259,10 @@ def rank_fused(user_emb, item_emb, users, targets, mask_rowptr, mask_items):
     score = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return rank, score
-    if mit.numel() == 0:
-        mit = torch.zeros(1, dtype=torch.int32, device=dev)
-    from . import engine
     splits = engine.load_library().lgcn_eval_splits(n, int(item_emb.shape[0]), _device_cus(dev))
     part = torch.empty(splits * n, dtype=torch.int32, device=dev)
-    _rank_launch(_rows(user_emb), _rows(item_emb), users, targets, mrow, mit, rank, score, part,
-                 splits)
+    _rank_launch(_rows(user_emb), _rows(item_emb), users, targets, mrow, _items_to_pass(mit), rank,
+                 score, part, splits)
     return rank, score
 
 
@@ -360,7 +355,6 @@ class Evaluator:
         rowptr, it = mask_csr(users, items, num_users)
         dev = self._device(device)
         if dev.type == "cuda":
-            from . import engine
             engine.load_library()  # a missing kernel is an error, here and not at the first call
         self._init(torch.from_numpy(rowptr).to(dev),
                    torch.from_numpy(np.ascontiguousarray(it, dtype=np.int32)).to(dev), num_users,
@@ -374,9 +368,7 @@ class Evaluator:
         return dev
 
     def _init(self, rowptr, items, num_users, num_items, dev):
-        if items.numel() == 0:  # a pointer to pass when every list is empty
-            items = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._rowptr, self._items = rowptr, items
+        self._rowptr, self._items = rowptr, _items_to_pass(items)
         self.num_users, self.num_items, self.device = num_users, num_items, dev
 
     @classmethod
@@ -395,7 +387,6 @@ class Evaluator:
         propagation under no_grad in model.eval() (left in eval mode, as main.py's evaluate leaves
         it), then one lgcn_score_rank per batch on views of the device-resident users and targets.
         No read-back. A pair outside [0, num_users) x [0, num_items) ranks -1."""
-        from .engine import LgcnError
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("Evaluator.ranks: batch_size must be positive")
@@ -404,10 +395,11 @@ class Evaluator:
             ue, ie = model(adj)[:2]
             _check_tables(ue, ie)
             if ie.device != self.device:
-                raise LgcnError(f"Evaluator on {self.device}, the model's tables on {ie.device}")
+                raise engine.LgcnError(f"Evaluator on {self.device}, the model's tables on "
+                                       f"{ie.device}")
             if ue.shape[0] != self.num_users or ie.shape[0] != self.num_items:
-                raise LgcnError(f"Evaluator for {self.num_users} x {self.num_items}, the model's "
-                                f"tables are {ue.shape[0]} x {ie.shape[0]}")
+                raise engine.LgcnError(f"Evaluator for {self.num_users} x {self.num_items}, the "
+                                       f"model's tables are {ue.shape[0]} x {ie.shape[0]}")
             if not (ie.is_cuda and ie.shape[1] in FUSED_DIMS):
                 return rank_torch(ue, ie, eval_users, eval_items, self._rowptr, self._items,
                                   min(batch_size, 1024))[0]
@@ -417,7 +409,6 @@ class Evaluator:
             rank = torch.empty(n, dtype=torch.int32, device=self.device)
             if n == 0:
                 return rank
-            from . import engine
             lib = engine.load_library()
             score = torch.empty(n, dtype=torch.float32, device=self.device)
             cus = _device_cus(self.device)

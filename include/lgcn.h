@@ -752,7 +752,8 @@ int lgcn_fusion_prelayer(const float* id_emb, int64_t ld_id, const float* conten
                          void* stream);
 
 /* ---- evaluation (main.py:404-439) ----------------------------------------------------------- */
-/* Item splits for lgcn_score_topk: ~2 blocks per CU, >= 2048 items per split, <= 256. */
+/* Item splits for lgcn_score_topk and lgcn_score_rank: ~2 blocks per CU, >= 2048 items per split,
+ * <= 256. */
 int lgcn_eval_splits(int32_t n_users, int32_t n_items, int32_t n_cu);
 
 /* Fused score + train-item mask + top-k for a batch of users (main.py:420-426) without the

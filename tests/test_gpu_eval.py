@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from eval_cases import assert_exact, dev as _dev, few_bits, random_mask, score_topk
 from gcn_recommendation_amd import engine, evaluate as E
 from util import MASKED, masked_scores64, topk_total_order
 
@@ -31,53 +32,6 @@ pytestmark = pytest.mark.gpu
 # ----------------------------------------------------------------------------------------------
 # helpers
 # ----------------------------------------------------------------------------------------------
-def _few_bits(rng, n, d, lim=4, den=8.0):
-    """Integers in [-lim, lim] / den as fp32 (tests/test_gpu_exact.py's "few_bits")."""
-    return (rng.integers(-lim, lim + 1, (n, d)) / den).astype(np.float32)
-
-
-def _random_mask(rng, n_users, n_items, per_user=4):
-    n = per_user * n_users
-    return E.mask_csr(rng.integers(0, n_users, n), rng.integers(0, n_items, n), n_users)
-
-
-def _dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _score_topk(dev, ue, ie, users, mrow, mit, k, n_splits, n_items=None):
-    """lgcn_score_topk through the C ABI on device tensors ue / ie (row views allowed: their
-    row strides are ld_u / ld_i). Every output and scratch element starts as a poison value, so
-    anything the kernel leaves unwritten shows. Returns host (top_scores, top_idx)."""
-    lib = engine.load_library()
-    d = ie.shape[1]
-    assert ue.shape[1] == d and ue.stride(1) == 1 and ie.stride(1) == 1
-    n_items = ie.shape[0] if n_items is None else n_items
-    users_t = _dev(np.asarray(users, dtype=np.int32), dev)
-    n = int(users_t.numel())
-    mrow_t = _dev(np.asarray(mrow, dtype=np.int32), dev)
-    mit_t = _dev(np.asarray(mit, dtype=np.int32), dev) if len(mit) else \
-        torch.zeros(1, dtype=torch.int32, device=dev)
-    part_s = torch.full((n_splits, n, k), float("nan"), dtype=torch.float32, device=dev)
-    part_i = torch.full((n_splits, n, k), -7, dtype=torch.int32, device=dev)
-    top_s = torch.full((n, k), float("nan"), dtype=torch.float32, device=dev)
-    top_i = torch.full((n, k), -7, dtype=torch.int32, device=dev)
-    P = engine._ptr
-    with torch.cuda.device(dev):
-        rc = lib.lgcn_score_topk(P(ue), ue.stride(0), P(users_t), n, P(ie), ie.stride(0),
-                                 n_items, d, P(mrow_t), P(mit_t), k, n_splits, P(part_s),
-                                 P(part_i), P(top_s), P(top_i), engine._stream(dev))
-        assert rc == 0, rc
-        torch.cuda.synchronize(dev)
-    return top_s.cpu().numpy(), top_i.cpu().numpy()
-
-
-def _assert_exact(scores64):
-    """The premise of part A: every score is an fp32 number (so, with the inputs' few bits, is
-    every partial sum in any order: the reference is the one right answer)."""
-    assert np.array_equal(scores64.astype(np.float32).astype(np.float64), scores64)
-
-
 def _assert_bitwise(got, ref, what=""):
     """got: the kernel's (scores fp32, idx int32); ref: the reference's (float64, int64)."""
     (gs, gi), (rs, ri) = got, ref
@@ -94,9 +48,9 @@ def _assert_bitwise(got, ref, what=""):
 def _check_exact(dev, ue, ie, users, mrow, mit, k, n_splits, what=""):
     """One exact case end to end; returns the kernel's output and the reference's."""
     full = masked_scores64(ue, ie, users, mrow, mit)
-    _assert_exact(full)
+    assert_exact(full)
     ref = topk_total_order(full, k)
-    got = _score_topk(dev, _dev(ue, dev), _dev(ie, dev), users, mrow, mit, k, n_splits)
+    got = score_topk(dev, _dev(ue, dev), _dev(ie, dev), users, mrow, mit, k, n_splits)
     _assert_bitwise(got, ref, what)
     return got, ref
 
@@ -108,9 +62,9 @@ def _check_exact(dev, ue, ie, users, mrow, mit, k, n_splits, what=""):
 def _widths_case(d):
     rng = np.random.default_rng(100 + d)
     n_table, n_items = 200, 2100
-    ue, ie = _few_bits(rng, n_table, d), _few_bits(rng, n_items, d)
+    ue, ie = few_bits(rng, n_table, d), few_bits(rng, n_items, d)
     users = rng.permutation(n_table)[:150]
-    mrow, mit = _random_mask(rng, n_table, n_items)
+    mrow, mit = random_mask(rng, n_table, n_items)
     full = masked_scores64(ue, ie, users, mrow, mit)
     full.setflags(write=False)
     first = topk_total_order(full, 33)[0]  # ties are what this input is for
@@ -123,8 +77,8 @@ def _widths_case(d):
 @pytest.mark.parametrize("d", [32, 64, 128, 256])
 def test_exact_widths_and_k(gpu_device, d, k, n_splits):
     ue, ie, users, mrow, mit, full = _widths_case(d)
-    _assert_exact(full)
-    got = _score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit, k,
+    assert_exact(full)
+    got = score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit, k,
                       n_splits)
     _assert_bitwise(got, topk_total_order(full, k), f"d={d} k={k} splits={n_splits}")
 
@@ -135,7 +89,7 @@ def test_exact_widths_and_k(gpu_device, d, k, n_splits):
 @functools.lru_cache(maxsize=None)
 def _geometry_tables():
     rng = np.random.default_rng(7)
-    return _few_bits(rng, 40, 64), _few_bits(rng, 2049, 64), rng.permutation(40)[:37]
+    return few_bits(rng, 40, 64), few_bits(rng, 2049, 64), rng.permutation(40)[:37]
 
 
 @pytest.mark.parametrize("n_splits", [1, 2, 5, 256])
@@ -143,7 +97,7 @@ def _geometry_tables():
 def test_exact_split_geometry(gpu_device, n_items, n_splits):
     ue, ie, users = _geometry_tables()
     k = 20
-    mrow, mit = _random_mask(np.random.default_rng(n_items), 40, n_items, 2 if n_items > 1 else 1)
+    mrow, mit = random_mask(np.random.default_rng(n_items), 40, n_items, 2 if n_items > 1 else 1)
     (gs, gi), _ = _check_exact(gpu_device, ue, ie[:n_items], users, mrow, mit, k, n_splits,
                                f"items={n_items} splits={n_splits}")
     if n_items < k:  # the tail past the last item
@@ -154,7 +108,7 @@ def test_exact_split_geometry(gpu_device, n_items, n_splits):
 def test_exact_most_splits_at_largest_k(gpu_device):
     """Both limits of the merge at once: 256 splits x k = 32 candidates per user."""
     ue, ie, users = _geometry_tables()
-    mrow, mit = _random_mask(np.random.default_rng(1), 40, 2049)
+    mrow, mit = random_mask(np.random.default_rng(1), 40, 2049)
     _check_exact(gpu_device, ue, ie, users, mrow, mit, 32, 256)
 
 
@@ -164,7 +118,7 @@ def test_no_items_at_all(gpu_device, n_splits):
     ie = torch.zeros((1, 64), device=gpu_device)  # a table to point at; none of it is an item
     mrow = np.zeros(41, np.int32)
     for users in ([3], [5, 0, 5]):
-        gs, gi = _score_topk(gpu_device, _dev(ue, gpu_device), ie, users, mrow, [], 20, n_splits,
+        gs, gi = score_topk(gpu_device, _dev(ue, gpu_device), ie, users, mrow, [], 20, n_splits,
                              n_items=0)
         assert gi.shape == (len(users), 20) and (gi == -1).all() and np.isneginf(gs).all()
 
@@ -176,8 +130,8 @@ def test_no_items_at_all(gpu_device, n_splits):
 @pytest.mark.parametrize("n_users", [1, 31, 32, 33, 127, 128, 129])
 def test_exact_user_geometry(gpu_device, n_users, n_splits):
     rng = np.random.default_rng(21)
-    ue, ie = _few_bits(rng, 60, 64), _few_bits(rng, 700, 64)
-    mrow, mit = _random_mask(rng, 60, 700)
+    ue, ie = few_bits(rng, 60, 64), few_bits(rng, 700, 64)
+    mrow, mit = random_mask(rng, 60, 700)
     users = np.random.default_rng(n_users).integers(0, 60, n_users)
     if n_users > 1:
         users[-1] = users[0]  # a repeat across the batch's two ends (other waves / blocks)
@@ -223,7 +177,7 @@ def test_exact_monotone_scores(gpu_device, direction, k, n_splits):
     assert n_items % 32
     ie = np.zeros((n_items, d), np.float32)
     ie[:, f] = np.arange(n_items) * 2.0 ** -4          # item j scores j/16 per unit of u[f]
-    ue = _few_bits(rng, n_users, d)                    # (the other features meet zeros)
+    ue = few_bits(rng, n_users, d)                    # (the other features meet zeros)
     sign = {"rising": np.ones(n_users), "falling": -np.ones(n_users),
             "mixed": np.where(np.arange(n_users) % 2, 1.0, -1.0)}[direction]
     ue[:, f] = sign * (1 + np.arange(n_users) % 3)
@@ -250,7 +204,7 @@ def test_exact_mask_edges(gpu_device, n_splits):
     rng = np.random.default_rng(44)
     n_users, n_items, d, k = 7, 300, 64, 20
     split0 = 160  # two splits of 300 items: ceil(300 / 2) rounded up to the 32-item tile
-    ue, ie = _few_bits(rng, n_users, d), _few_bits(rng, n_items, d)
+    ue, ie = few_bits(rng, n_users, d), few_bits(rng, n_items, d)
     # item 0 is user 5's single best item and the last item user 6's (|item features| <= 1/2)
     ie[0] = np.where(ue[5] < 0, -0.5, 0.5)
     ie[-1] = np.where(ue[6] < 0, -0.5, 0.5)
@@ -364,8 +318,8 @@ def test_exact_row_strides(gpu_device, d):
     """ld_u = d + 4 and ld_i = 2d: views of wider tables that hold NaN outside the view."""
     rng = np.random.default_rng(66 + d)
     n_table, n_items, k = 50, 777, 20
-    ue, ie = _few_bits(rng, n_table, d), _few_bits(rng, n_items, d)
-    mrow, mit = _random_mask(rng, n_table, n_items)
+    ue, ie = few_bits(rng, n_table, d), few_bits(rng, n_items, d)
+    mrow, mit = random_mask(rng, n_table, n_items)
     users = rng.integers(0, n_table, 45)
     wide_u = torch.full((n_table, d + 4), float("nan"), device=gpu_device)
     wide_i = torch.full((n_items, 2 * d), float("nan"), device=gpu_device)
@@ -374,9 +328,9 @@ def test_exact_row_strides(gpu_device, d):
     vu, vi = wide_u[:, 4:], wide_i[:, d:]
     assert vu.stride(0) == d + 4 and vi.stride(0) == 2 * d and not vu.is_contiguous()
     full = masked_scores64(ue, ie, users, mrow, mit)
-    _assert_exact(full)
+    assert_exact(full)
     for n_splits in (1, 3):
-        got = _score_topk(gpu_device, vu, vi, users, mrow, mit, k, n_splits)
+        got = score_topk(gpu_device, vu, vi, users, mrow, mit, k, n_splits)
         _assert_bitwise(got, topk_total_order(full, k), f"d={d} splits={n_splits}")
 
 
@@ -385,14 +339,14 @@ def test_exact_tables_in_one_allocation(gpu_device):
     table: users first, items after)."""
     rng = np.random.default_rng(77)
     U, I, d, k = 50, 900, 64, 20
-    table = _few_bits(rng, U + I + 30, d)  # (rows past the items: never an item)
-    mrow, mit = _random_mask(rng, U, I)
+    table = few_bits(rng, U + I + 30, d)  # (rows past the items: never an item)
+    mrow, mit = random_mask(rng, U, I)
     users = rng.permutation(U)
     full = masked_scores64(table[:U], table[U:U + I], users, mrow, mit)
-    _assert_exact(full)
+    assert_exact(full)
     t = _dev(table, gpu_device)
     for n_splits in (1, 2):
-        got = _score_topk(gpu_device, t[:U], t[U:], users, mrow, mit, k, n_splits, n_items=I)
+        got = score_topk(gpu_device, t[:U], t[U:], users, mrow, mit, k, n_splits, n_items=I)
         _assert_bitwise(got, topk_total_order(full, k), f"splits={n_splits}")
 
 
@@ -405,7 +359,7 @@ def _gauss_case(d):
     n_table, n_items = 350, 4000
     ue = rng.standard_normal((n_table, d)).astype(np.float32)
     ie = rng.standard_normal((n_items, d)).astype(np.float32)
-    mrow, mit = _random_mask(rng, n_table, n_items, 10)
+    mrow, mit = random_mask(rng, n_table, n_items, 10)
     users = rng.permutation(n_table)[:300]
     full = masked_scores64(ue, ie, users, mrow, mit)
     masked = np.zeros(full.shape, bool)
@@ -426,7 +380,7 @@ def test_gaussian_lists_within_rounding(gpu_device, d, n_splits):
     k = 20
     n, n_items = full.shape
     assert (~masked).sum(1).min() >= k
-    gs, gi = _score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit,
+    gs, gi = score_topk(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, mrow, mit,
                          k, n_splits)
     rows = np.arange(n)[:, None]
     # distinct and in range
@@ -456,7 +410,7 @@ def test_gaussian_bits_do_not_depend_on_splits_slots_or_runs(gpu_device, d):
     uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
 
     def run(us, n_splits):
-        gs, gi = _score_topk(gpu_device, uet, iet, us, mrow, mit, 20, n_splits)
+        gs, gi = score_topk(gpu_device, uet, iet, us, mrow, mit, 20, n_splits)
         return gs.view(np.uint32), gi
 
     s1, i1 = run(users, 1)
@@ -498,12 +452,12 @@ def test_python_evaluation_agrees_with_reference_lists(gpu_device, d):
     rng = np.random.default_rng(1200 + d)
     U, I, k = 180, 1500, 20
     lim = {64: 8, 12: 16}[d]  # coarse enough for ties at the k-th place, fine enough for none
-    ue, ie = _few_bits(rng, U, d, lim, 2.0 * lim), _few_bits(rng, I, d, lim, 2.0 * lim)
+    ue, ie = few_bits(rng, U, d, lim, 2.0 * lim), few_bits(rng, I, d, lim, 2.0 * lim)
     tu, ti = rng.integers(0, U, 6 * U), rng.integers(0, I, 6 * U)
     mrow, mit = E.mask_csr(tu, ti, U)
     users = rng.permutation(U)[:150]  # evaluate takes each user once (a dict)
     full = masked_scores64(ue, ie, users, mrow, mit)
-    _assert_exact(full)
+    assert_exact(full)
     rs, ri = topk_total_order(full, k + 1)
     no_tie_at_k = rs[:, k - 1] > rs[:, k]
     no_tie = (rs[:, :-1] > rs[:, 1:]).all(1)

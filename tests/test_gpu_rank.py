@@ -1,6 +1,6 @@
 """The rank evaluation kernel lgcn_score_rank (gcn_recommendation_amd/csrc/lgcn_eval.hip: the
 target's score from a gathered MFMA tile, an integer count per (user, item split) in the tile
-loop, the train-item correction from gathered tiles) against tests/rank_cases.py's rank_ref on
+loop, the train-item correction from gathered tiles) against tests/eval_cases.py's rank_ref on
 tests/util.py's float64 masked scores:
 
     rank_ref[b] = #{i != t : s[b,i] > s[b,t] or (s[b,i] == s[b,t] and i < t)}
@@ -23,71 +23,17 @@ import pytest
 import torch
 
 from conftest import Cfg
+from eval_cases import (assert_exact, dev as _dev, few_bits, random_mask, rank_ref, score_rank,
+                        score_topk)
 from gcn_recommendation_amd import engine, evaluate as E, graph, sampler
-from rank_cases import assert_exact, few_bits, random_mask, rank_ref
 from util import MASKED, masked_scores64, topk_total_order
 
 pytestmark = pytest.mark.gpu
-
-POISON_RANK, POISON_SCORE = -7, 12345.0
 
 
 # ----------------------------------------------------------------------------------------------
 # helpers
 # ----------------------------------------------------------------------------------------------
-def _dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _score_rank(dev, ue, ie, users, targets, mrow, mit, n_splits, n_items=None):
-    """lgcn_score_rank through the C ABI on device tensors ue / ie (row views allowed: their row
-    strides are ld_u / ld_i). Returns host (rank int32 [n], target_score fp32 [n])."""
-    lib = engine.load_library()
-    d = ie.shape[1]
-    assert ue.shape[1] == d and ue.stride(1) == 1 and ie.stride(1) == 1
-    n_items = ie.shape[0] if n_items is None else n_items
-    users_t = _dev(np.asarray(users, dtype=np.int32), dev)
-    targets_t = _dev(np.asarray(targets, dtype=np.int32), dev)
-    n = int(users_t.numel())
-    assert targets_t.numel() == n
-    mrow_t = _dev(np.asarray(mrow, dtype=np.int32), dev)
-    mit_t = _dev(np.asarray(mit, dtype=np.int32), dev) if len(mit) else \
-        torch.zeros(1, dtype=torch.int32, device=dev)
-    part = torch.full((n_splits, n), POISON_RANK, dtype=torch.int32, device=dev)
-    score = torch.full((n,), POISON_SCORE, dtype=torch.float32, device=dev)
-    rank = torch.full((n,), POISON_RANK, dtype=torch.int32, device=dev)
-    P = engine._ptr
-    with torch.cuda.device(dev):
-        rc = lib.lgcn_score_rank(P(ue), ue.stride(0), P(users_t), n, P(ie), ie.stride(0), n_items,
-                                 d, P(mrow_t), P(mit_t), P(targets_t), n_splits, P(part), P(score),
-                                 P(rank), engine._stream(dev))
-        assert rc == 0, rc
-        torch.cuda.synchronize(dev)
-    assert (part.cpu().numpy() >= 0).all()  # every split wrote every slot
-    return rank.cpu().numpy(), score.cpu().numpy()
-
-
-def _score_topk(dev, ue, ie, users, mrow, mit, k, n_splits):
-    lib = engine.load_library()
-    d = ie.shape[1]
-    users_t = _dev(np.asarray(users, dtype=np.int32), dev)
-    n = int(users_t.numel())
-    mrow_t = _dev(np.asarray(mrow, dtype=np.int32), dev)
-    mit_t = _dev(np.asarray(mit, dtype=np.int32), dev)
-    part_s = torch.full((n_splits, n, k), float("nan"), dtype=torch.float32, device=dev)
-    part_i = torch.full((n_splits, n, k), -7, dtype=torch.int32, device=dev)
-    top_s = torch.full((n, k), float("nan"), dtype=torch.float32, device=dev)
-    top_i = torch.full((n, k), -7, dtype=torch.int32, device=dev)
-    P = engine._ptr
-    with torch.cuda.device(dev):
-        rc = lib.lgcn_score_topk(P(ue), ue.stride(0), P(users_t), n, P(ie), ie.stride(0),
-                                 ie.shape[0], d, P(mrow_t), P(mit_t), k, n_splits, P(part_s),
-                                 P(part_i), P(top_s), P(top_i), engine._stream(dev))
-        assert rc == 0, rc
-        torch.cuda.synchronize(dev)
-    return top_s.cpu().numpy(), top_i.cpu().numpy()
-
-
 def _assert_ranks(got, full, targets, what=""):
     """got: the kernel's (rank int32, target_score fp32); full: the float64 masked scores."""
     rank, score = got
@@ -109,7 +55,7 @@ def _assert_ranks(got, full, targets, what=""):
 def _check_exact(dev, ue, ie, users, targets, mrow, mit, n_splits, what=""):
     full = masked_scores64(ue, ie, users, mrow, mit)
     assert_exact(full)
-    got = _score_rank(dev, _dev(ue, dev), _dev(ie, dev), users, targets, mrow, mit, n_splits)
+    got = score_rank(dev, _dev(ue, dev), _dev(ie, dev), users, targets, mrow, mit, n_splits)
     return got, _assert_ranks(got, full, targets, what), full
 
 
@@ -151,7 +97,7 @@ def _widths_case(d):
 def test_exact_widths(gpu_device, d, n_splits):
     ue, ie, users, targets, mrow, mit, full = _widths_case(d)
     assert_exact(full)
-    got = _score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets, mrow,
+    got = score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets, mrow,
                       mit, n_splits)
     want = _assert_ranks(got, full, targets, f"d={d} splits={n_splits}")
     assert (want < 40).sum() >= 60 and (want > 200).sum() >= 30
@@ -184,7 +130,7 @@ def test_no_items_at_all(gpu_device, n_splits):
     ue, _, _ = _geometry_tables()
     ie = torch.zeros((1, 64), device=gpu_device)  # a table to point at; none of it is an item
     mrow = np.zeros(41, np.int32)
-    rank, score = _score_rank(gpu_device, _dev(ue, gpu_device), ie, [3, 5, 0, 5], [0, -1, 1, 7],
+    rank, score = score_rank(gpu_device, _dev(ue, gpu_device), ie, [3, 5, 0, 5], [0, -1, 1, 7],
                               mrow, [], n_splits, n_items=0)
     assert rank.tolist() == [-1] * 4 and np.isnan(score).all()
 
@@ -299,7 +245,7 @@ def test_exact_mask_edges(gpu_device, n_splits):
     assert rank[8] == 0 and score[8] == np.float32(free[6, order[6, 7]])
     assert rank[9] == 0
     # every list empty, mask_items a one-element dummy
-    got = _score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets,
+    got = score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets,
                       nothing[0], [], n_splits)
     _assert_ranks(got, masked_scores64(ue, ie, users, *nothing), targets, "no train item")
 
@@ -361,7 +307,7 @@ def test_exact_row_strides(gpu_device, d):
     assert_exact(full)
     targets = _mixed_targets(rng, full)
     for n_splits in (1, 3):
-        got = _score_rank(gpu_device, vu, vi, users, targets, mrow, mit, n_splits)
+        got = score_rank(gpu_device, vu, vi, users, targets, mrow, mit, n_splits)
         _assert_ranks(got, full, targets, f"d={d} splits={n_splits}")
 
 
@@ -378,7 +324,7 @@ def test_exact_tables_in_one_allocation(gpu_device):
     targets = _mixed_targets(rng, full)
     t = _dev(table, gpu_device)
     for n_splits in (1, 2):
-        got = _score_rank(gpu_device, t[:U], t[U:], users, targets, mrow, mit, n_splits, n_items=I)
+        got = score_rank(gpu_device, t[:U], t[U:], users, targets, mrow, mit, n_splits, n_items=I)
         _assert_ranks(got, full, targets, f"splits={n_splits}")
 
 
@@ -392,7 +338,7 @@ def test_targets_outside_the_table(gpu_device, n_splits):
     targets = targets.copy()
     out = np.array([0, 5, 31, 32, 33, 100, 149])  # among slots that keep their targets
     targets[out] = [-1, n_items, -1, n_items, -(2 ** 31), 2 ** 31 - 1, n_items + 31]
-    got = _score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets, mrow,
+    got = score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users, targets, mrow,
                       mit, n_splits)
     want = _assert_ranks(got, full, targets)
     assert (want[out] == -1).all() and (np.delete(want, out) >= 0).all()
@@ -453,8 +399,8 @@ def test_gaussian_rank_is_the_place_in_the_topk_list(gpu_device, d):
     want = rank_ref(full, targets)
     assert (want < 32).sum() * 3 >= len(want) and (want >= 32).sum() * 3 >= len(want)
     uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
-    rank, score = _score_rank(gpu_device, uet, iet, users, targets, mrow, mit, 3)
-    ts, ti = _score_topk(gpu_device, uet, iet, users, mrow, mit, 32, 2)
+    rank, score = score_rank(gpu_device, uet, iet, users, targets, mrow, mit, 3)
+    ts, ti = score_topk(gpu_device, uet, iet, users, mrow, mit, 32, 2)
     hit = ti == targets[:, None]
     listed = hit.any(1)
     place = hit.argmax(1)
@@ -471,7 +417,7 @@ def test_gaussian_rank_within_rounding(gpu_device, d, n_splits):
     ue, ie, users, targets, mrow, mit, full, masked, tau = _gauss_case(d)
     lo, hi = _interval(full, tau, targets)
     assert (lo <= hi).all() and (lo == hi).sum() * 2 >= len(lo)  # the bound cannot hide a count
-    rank, score = _score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users,
+    rank, score = score_rank(gpu_device, _dev(ue, gpu_device), _dev(ie, gpu_device), users,
                               targets, mrow, mit, n_splits)
     assert ((lo <= rank) & (rank <= hi)).all(), np.nonzero((rank < lo) | (rank > hi))[0]
     rows = np.arange(len(targets))
@@ -485,7 +431,7 @@ def test_gaussian_bits_do_not_depend_on_splits_slots_or_runs(gpu_device, d):
     uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
 
     def run(sel, n_splits):
-        r, s = _score_rank(gpu_device, uet, iet, users[sel], targets[sel], mrow, mit, n_splits)
+        r, s = score_rank(gpu_device, uet, iet, users[sel], targets[sel], mrow, mit, n_splits)
         return r, s.view(np.uint32)
 
     everyone = np.arange(len(users))
@@ -506,7 +452,7 @@ def test_gaussian_bits_do_not_depend_on_splits_slots_or_runs(gpu_device, d):
 def test_rank_fused_is_the_abi_call(gpu_device):
     ue, ie, users, targets, mrow, mit, full = _widths_case(64)
     uet, iet = _dev(ue, gpu_device), _dev(ie, gpu_device)
-    want = _score_rank(gpu_device, uet, iet, users, targets, mrow, mit, 2)
+    want = score_rank(gpu_device, uet, iet, users, targets, mrow, mit, 2)
     _assert_ranks(want, full, targets)
     mrow_t, mit_t = _dev(mrow, gpu_device), _dev(mit, gpu_device)
     for us, ts_, mr, mi in ((users, targets, mrow, mit),

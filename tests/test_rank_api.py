@@ -1,6 +1,6 @@
 """The rank evaluation without a GPU (gcn_recommendation_amd/evaluate.py: metrics_from_ranks,
 rank_torch, Evaluator on a CPU device; lgcn_score_rank's host-side validation): the metrics
-against values worked out by hand, rank_torch against tests/rank_cases.py's rank_ref on float64
+against values worked out by hand, rank_torch against tests/eval_cases.py's rank_ref on float64
 scores, the Evaluator end to end against a loop written after main.py:404-439, and everything the
 Python layer and the C entry point refuse before a launch."""
 import ctypes
@@ -11,8 +11,8 @@ import pytest
 import torch
 
 from conftest import Cfg
+from eval_cases import assert_exact, few_bits, random_mask, rank_ref
 from gcn_recommendation_amd import _build, engine, evaluate as E, graph, sampler
-from rank_cases import assert_exact, few_bits, random_mask, rank_ref
 from util import MASKED, masked_scores64
 
 EINVAL, EALIGN = -1, -2  # include/lgcn.h

@@ -18,14 +18,25 @@ distribution only through the first tiles). Checked before timing: for every slo
 in the top-20 list the rank is its place there and the score is the list's, bit for bit; every
 other rank is >= 20; both passes return the same recall@20 / ndcg@20.
 
+With --against PATH (another build of the library with the same ABI, such as the parent commit's
+under gcn_recommendation_amd/_variants/) the tool compares the two builds instead of the two
+passes: both are loaded into this process and run lgcn_score_topk and lgcn_score_rank on the same
+batch, tables, mask and split count, each into outputs of its own. First top_scores, top_idx, rank
+and target_score of the two builds must be equal as raw bits, here and on the Gaussian tables of
+tests/test_gpu_eval.py at d = 32, 128, 256 (a reordered score chain shows nowhere else); then the
+four calls are timed between events, PATH's and the tree's alternating, and for each entry point
+the tree's median may exceed PATH's by no more than PATH's own interquartile range.
+
 Prints one JSON line on stdout (progress goes to stderr).
 
     timeout -k 10 840 python tools/eval_rank_bench.py [--config c3] [--reps 9] [--heldout 65536]
+    timeout -k 10 600 python tools/eval_rank_bench.py --against PATH [--reps 9]
 
 One process, so every figure comes from one machine in one run; it holds the GPU for the whole of
 it and is therefore started under a time limit of its own, as every GPU step is.
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -70,6 +81,125 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+class Calls:
+    """lgcn_score_topk (k) and lgcn_score_rank of one build of the library on shared inputs, with
+    outputs and scratch of its own."""
+
+    def __init__(self, lib, ue, ie, users, mrow, mit, k, splits):
+        dev, n = ie.device, int(users.numel())
+        self.lib, self.inputs, self.k, self.splits = lib, (ue, ie, users, mrow, mit), k, splits
+        self.part_s = torch.empty((splits, n, k), dtype=torch.float32, device=dev)
+        self.part_i = torch.empty((splits, n, k), dtype=torch.int32, device=dev)
+        self.top_s = torch.empty((n, k), dtype=torch.float32, device=dev)
+        self.top_i = torch.empty((n, k), dtype=torch.int32, device=dev)
+        self.part = torch.empty(splits * n, dtype=torch.int32, device=dev)
+        self.rank_out = torch.empty(n, dtype=torch.int32, device=dev)
+        self.score = torch.empty(n, dtype=torch.float32, device=dev)
+        self.targets = None
+
+    def topk(self):
+        ue, ie, users, mrow, mit = self.inputs
+        P = engine._ptr
+        engine._check(self.lib.lgcn_score_topk(
+            P(ue), ue.stride(0), P(users), int(users.numel()), P(ie), ie.stride(0), ie.shape[0],
+            ie.shape[1], P(mrow), P(mit), self.k, self.splits, P(self.part_s), P(self.part_i),
+            P(self.top_s), P(self.top_i), engine._stream(ie.device)), "lgcn_score_topk")
+
+    def rank(self):
+        ue, ie, users, mrow, mit = self.inputs
+        P = engine._ptr
+        engine._check(self.lib.lgcn_score_rank(
+            P(ue), ue.stride(0), P(users), int(users.numel()), P(ie), ie.stride(0), ie.shape[0],
+            ie.shape[1], P(mrow), P(mit), P(self.targets), self.splits, P(self.part),
+            P(self.score), P(self.rank_out), engine._stream(ie.device)), "lgcn_score_rank")
+
+    def outputs(self):
+        return {"top_scores": self.top_s, "top_idx": self.top_i, "rank": self.rank_out,
+                "target_score": self.score}
+
+
+def load_build(path):
+    """Another build of the library beside the tree's, bound to the same ABI."""
+    lib = ctypes.CDLL(path)
+    for name, res, argtypes in engine.ABI:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, argtypes
+    if lib.lgcn_abi_version() != engine.ABI_VERSION:
+        sys.exit(f"eval_rank_bench: {path} has another ABI version")
+    return lib
+
+
+def same_bits(tree, other, what):
+    """Both builds' calls on their shared inputs (the targets: every other slot an item of the
+    tree's list): the four outputs equal as raw bits."""
+    tree.topk()
+    n, k = tree.top_i.shape
+    g = torch.Generator(device=tree.top_i.device)
+    g.manual_seed(11)
+    items = tree.inputs[1].shape[0]
+    targets = torch.randint(0, items, (n,), generator=g, device=tree.top_i.device,
+                            dtype=torch.int32)
+    place = torch.randint(0, k, (n, 1), generator=g, device=tree.top_i.device)
+    targets[::2] = tree.top_i.gather(1, place)[::2, 0]
+    tree.targets = other.targets = targets
+    for c in (other, tree):
+        c.topk()
+        c.rank()
+    torch.cuda.synchronize()
+    for name, t in tree.outputs().items():
+        o = other.outputs()[name]
+        assert torch.equal(t.view(torch.int32), o.view(torch.int32)), f"{what}: {name} differs"
+    bench.log(f"[eval_rank_bench] {what}: top_scores, top_idx, rank, target_score bit-equal")
+
+
+def gaussian_bits(lib, other, dev, k):
+    """same_bits on the tables of tests/test_gpu_eval.py's Gaussian case (300 users x 4000 items),
+    the widths C3 does not have."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_eval import _gauss_case
+    checked = []
+    for d in (32, 128, 256):
+        ue, ie, users, mrow, mit = (torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                                    for a in _gauss_case(d)[:5])
+        for splits in (1, 4):
+            args = (ue, ie, users.int(), mrow, mit, k, splits)
+            same_bits(Calls(lib, *args), Calls(other, *args), f"gaussian d={d} splits={splits}")
+            checked.append([d, splits])
+    return checked
+
+
+def against(args, config, tree):
+    """The --against comparison on the batch of `tree` (the tree's build): the result line."""
+    ie, users = tree.inputs[1:3]
+    other_lib = load_build(args.against)
+    other = Calls(other_lib, *tree.inputs, tree.k, tree.splits)
+    same_bits(tree, other, f"{config} d={ie.shape[1]}")
+    times = {"topk": ([], []), "rank": ([], [])}  # (PATH's, the tree's)
+    for _ in range(args.reps):  # alternating: both builds see the same machine state
+        for name in times:
+            for c, t in zip((other, tree), times[name]):
+                t.append(event_ms(getattr(c, name)))
+    result = {"config": config, "users": int(users.numel()), "items": ie.shape[0],
+              "d": ie.shape[1], "k": tree.k, "splits": tree.splits,
+              "against": os.path.relpath(args.against, ROOT), "reps": args.reps,
+              "bit_equal": {args.config: True, "gaussian_d_splits":
+                            gaussian_bits(tree.lib, other_lib, ie.device, tree.k)}}
+    for name, (t_other, t_tree) in times.items():
+        lo, med, hi = (float(q) for q in np.percentile(t_other, [25, 50, 75]))
+        new_med = float(np.median(t_tree))
+        result[f"lgcn_score_{name}"] = {
+            "against_ms": round(med, 3), "tree_ms": round(new_med, 3),
+            "against_iqr_ms": round(hi - lo, 3), "within_against_iqr": new_med - med <= hi - lo,
+            "against_all": [round(x, 3) for x in t_other],
+            "tree_all": [round(x, 3) for x in t_tree]}
+        bench.log(f"[eval_rank_bench] lgcn_score_{name}: {med:.2f} ms against, {new_med:.2f} ms "
+                  f"tree, spread (IQR) of the former {hi - lo:.2f} ms")
+    result["what"] = ("one call each between events on one stream after one warm-up call each, "
+                      "PATH's build and the tree's alternating, medians of reps; same batch / "
+                      "tables / mask / splits; outputs compared as raw bits before timing")
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
@@ -78,6 +208,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--pass-reps", type=int, default=3)
     ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--against", metavar="PATH", help="compare with this build of the library")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("eval_rank_bench: needs a HIP device")
@@ -105,29 +236,18 @@ def main():
     n = min(args.users, U)
     users = torch.from_numpy(np.sort(rng.choice(U, n, replace=False)).astype(np.int32)).to(dev)
     splits = lib.lgcn_eval_splits(n, I, E._device_cus(dev))
-    part_s = torch.empty((splits, n, k), dtype=torch.float32, device=dev)
-    part_i = torch.empty((splits, n, k), dtype=torch.int32, device=dev)
-    top_s = torch.empty((n, k), dtype=torch.float32, device=dev)
-    top_i = torch.empty((n, k), dtype=torch.int32, device=dev)
-    part = torch.empty(splits * n, dtype=torch.int32, device=dev)
-    rank = torch.empty(n, dtype=torch.int32, device=dev)
-    score = torch.empty(n, dtype=torch.float32, device=dev)
-    P, stream = engine._ptr, engine._stream(dev)
-
-    def topk():
-        engine._check(lib.lgcn_score_topk(P(ue), d, P(users), n, P(ie), d, I, d, P(ev._rowptr),
-                                          P(ev._items), k, splits, P(part_s), P(part_i), P(top_s),
-                                          P(top_i), stream), "lgcn_score_topk")
-
+    tree = Calls(lib, ue, ie, users, ev._rowptr, ev._items, k, splits)
+    if args.against:
+        print(json.dumps(against(args, cfg["name"], tree)), flush=True)
+        return
+    top_s, top_i, rank, score = tree.outputs().values()
+    topk, rank_call = tree.topk, tree.rank
     topk()
     # targets: every other slot an item of its top-k list (a hit), the others anywhere
     targets = torch.from_numpy(rng.integers(0, I, n).astype(np.int32)).to(dev)
     place = torch.from_numpy(rng.integers(0, k, n)).to(dev)
     targets[::2] = top_i.gather(1, place[:, None])[::2, 0]
-
-    def rank_call():
-        E._rank_launch(ue, ie, users, targets, ev._rowptr, ev._items, rank, score, part, splits)
-
+    tree.targets = targets
     rank_call()
     torch.cuda.synchronize()
     hit = top_i == targets[:, None]
