@@ -28,3 +28,22 @@ extern "C" int lgcn_bpr_loss(const float* u, int64_t ldu, const float* p, int64_
     return lgcn_bpr::launch(rows, B, d, lambda, terms, loss, grads,
                             reinterpret_cast<hipStream_t>(stream));
 }
+
+// the same batch with the brand-preference term (main.py:382-391): eight gathered blocks
+extern "C" int lgcn_bpr_brand_loss(const float* u, int64_t ldu, const float* p, int64_t ldp,
+                                   const float* n, int64_t ldn, const float* u0, int64_t ldu0,
+                                   const float* p0, int64_t ldp0, const float* n0, int64_t ldn0,
+                                   const float* bp, int64_t ldbp, const float* bn, int64_t ldbn,
+                                   const uint8_t* brand_ok, int32_t B, int32_t d, float lambda,
+                                   float brand_weight, float* terms, float* loss, float* grads,
+                                   float* coef, void* stream) {
+    if (B < 1 || d < 1 || !loss || !terms || !grads) return LGCN_EINVAL;
+    if (!u || !p || !n || !u0 || !p0 || !n0 || !bp || !bn) return LGCN_EINVAL;
+    if (ldu < d || ldp < d || ldn < d || ldu0 < d || ldp0 < d || ldn0 < d || ldbp < d || ldbn < d)
+        return LGCN_EINVAL;
+    const lgcn_bpr::GatheredBrandRows rows = {{u, p, n, u0, p0, n0, bp, bn},
+                                              {ldu, ldp, ldn, ldu0, ldp0, ldn0, ldbp, ldbn},
+                                              brand_ok};
+    return lgcn_bpr::launch_brand(rows, B, d, lambda, brand_weight, terms, loss, grads, coef,
+                                  reinterpret_cast<hipStream_t>(stream));
+}

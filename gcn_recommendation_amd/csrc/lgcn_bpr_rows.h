@@ -1,6 +1,7 @@
 // lgcn_bpr_rows.h — the BPR batch kernels shared by lgcn_bpr.hip (rows given as gathered
 // [B x d] blocks) and lgcn_bpr_step.hip (rows read from the tables by index): one row kernel,
-// templated on how sample b's six row pointers are obtained, and the fixed-order batch reduction.
+// templated on how sample b's six row pointers are obtained, and the fixed-order batch reduction;
+// below them their siblings with the brand-preference term (eight rows per sample).
 //
 //   loss = -mean_b log(sigmoid(<u_b,p_b> - <u_b,n_b>) + 1e-8)
 //          + lambda * (|U0|^2 + |P0|^2 + |N0|^2) / B
@@ -161,6 +162,198 @@ inline int launch(const Rows& rows, int32_t B, int32_t d, float lambda, float* t
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_bpr_reduce, dim3(1), dim3(256), 0, s, terms, B, lambda, loss);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+// ---- the batch with the brand-preference term (main.py:382-391, 499-522) ------------------------
+//   loss = (bpr + w * -mean_b log(sigmoid(<u_b,bp_b> - <u_b,bn_b>) + 1e-8)) + reg
+// bp / bn = the final brand rows of the sample's positive / negative item. The brand term's chain
+// is the base one with -w/B for -1/B: c'_b = ((-w/B) / (s'_b + 1e-8)) * (1 - s'_b) * s'_b,
+// du += c'*bp + (-c')*bn, dbp = c'*u, dbn = (-c')*u. A sample without brand rows (kBase) has no
+// brand term: c' = 0, a zero log term, +0 brand gradient rows, and the base kernel's du.
+
+// the eight rows of one sample: SampleRows' six, then bp, bn (final brand rows)
+struct BrandSampleRows {
+    const float* r[8];
+};
+
+enum { kSkip = 0, kBase = 1, kBrand = 2 };  // what Rows::get found of a sample
+
+// rows of eight gathered blocks; brand_ok (NULL = every sample) tells per sample whether rows b of
+// the two brand blocks are its brand rows
+struct GatheredBrandRows {
+    const float* p[8];
+    int64_t ld[8];
+    const uint8_t* brand_ok;
+    __device__ __forceinline__ int get(int64_t b, BrandSampleRows& o) const {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o.r[i] = p[i] + b * ld[i];
+        return (brand_ok == nullptr || brand_ok[b]) ? kBrand : kBase;
+    }
+};
+
+// IndexedRows plus the final brand table fb, looked up through item_brand (int32 [n_items]; a
+// value outside [0, n_brands), -1 by convention, = the item has no brand)
+struct IndexedBrandRows {
+    IndexedRows base;
+    const float* fb;
+    int64_t ld_fb;
+    const int32_t* item_brand;
+    int64_t n_brands;
+    __device__ __forceinline__ int get(int64_t b, BrandSampleRows& o) const {
+        SampleRows s;
+        if (!base.get(b, s)) return kSkip;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) o.r[i] = s.r[i];
+        const int64_t rp = item_brand[base.pos[b]], rn = item_brand[base.neg[b]];
+        if (rp < 0 || rp >= n_brands || rn < 0 || rn >= n_brands) {
+            o.r[6] = o.r[7] = nullptr;
+            return kBase;
+        }
+        o.r[6] = fb + rp * ld_fb;
+        o.r[7] = fb + rn * ld_fb;
+        return kBrand;
+    }
+};
+
+// grads = [8 x B x d] in the order u0, p0, n0, u, p, n, bp, bn: the three layer-0 blocks, then the
+// five final-row blocks as one [5B x d] source of the scatter. terms = [3 x B] (log term, squared
+// norms, brand log term); coef (nullptr = not wanted) = [2 x B] (c, c'). The base quantities are
+// computed by k_bpr_rows' own expressions, in its order.
+template <typename Rows>
+__global__ __launch_bounds__(kWave * kRowsPerBlock) void k_bpr_brand_rows(
+    Rows rows, int32_t B, int32_t d, float lambda, float w, float* __restrict__ terms,
+    float* __restrict__ grads, float* __restrict__ coef) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t b = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x / kWave;
+    if (b >= B) return;
+    const int64_t bd = (int64_t)B * d;
+    float* gu0 = grads;
+    float* gp0 = grads + bd;
+    float* gn0 = grads + 2 * bd;
+    float* gu = grads + 3 * bd;
+    float* gp = grads + 4 * bd;
+    float* gn = grads + 5 * bd;
+    float* gbp = grads + 6 * bd;
+    float* gbn = grads + 7 * bd;
+    BrandSampleRows sr;
+    const int kind = rows.get(b, sr);
+    if (kind == kSkip) {
+        for (int k = lane; k < d; k += kWave) {
+            const int64_t o = b * (int64_t)d + k;
+            gu[o] = gp[o] = gn[o] = gu0[o] = gp0[o] = gn0[o] = gbp[o] = gbn[o] = 0.f;
+        }
+        if (lane == 0) {
+            terms[b] = terms[B + b] = terms[2 * (int64_t)B + b] = 0.f;
+            if (coef != nullptr) coef[b] = coef[B + b] = 0.f;
+        }
+        return;
+    }
+    const bool brand = kind == kBrand;
+    const float* ub = sr.r[0];
+    const float* pb = sr.r[1];
+    const float* nb = sr.r[2];
+    const float* ub0 = sr.r[3];
+    const float* pb0 = sr.r[4];
+    const float* nb0 = sr.r[5];
+    const float* bpb = sr.r[6];  // read only when brand
+    const float* bnb = sr.r[7];
+    float sp = 0.f, sn = 0.f, sq = 0.f, tp = 0.f, tn = 0.f;
+    for (int k = lane; k < d; k += kWave) {
+        const float x = ub[k];
+        sp = __builtin_fmaf(x, pb[k], sp);
+        sn = __builtin_fmaf(x, nb[k], sn);
+        sq = __builtin_fmaf(ub0[k], ub0[k], sq);
+        sq = __builtin_fmaf(pb0[k], pb0[k], sq);
+        sq = __builtin_fmaf(nb0[k], nb0[k], sq);
+        if (brand) {
+            tp = __builtin_fmaf(x, bpb[k], tp);
+            tn = __builtin_fmaf(x, bnb[k], tn);
+        }
+    }
+    sp = wave_sum(sp);
+    sn = wave_sum(sn);
+    sq = wave_sum(sq);
+    tp = wave_sum(tp);
+    tn = wave_sum(tn);
+    const float x = sp - sn;
+    const float s = 1.f / (1.f + expf(-x));
+    const float c = ((-1.f / (float)B) / (s + 1e-8f)) * (1.f - s) * s;
+    const float r = 2.f * lambda / (float)B;
+    float cb = 0.f, lb = 0.f;
+    if (brand) {
+        const float xb = tp - tn;
+        const float sb = 1.f / (1.f + expf(-xb));
+        cb = ((-w / (float)B) / (sb + 1e-8f)) * (1.f - sb) * sb;
+        lb = logf(sb + 1e-8f);
+    }
+    for (int k = lane; k < d; k += kWave) {
+        const int64_t o = b * (int64_t)d + k;
+        const float base = c * pb[k] + (-c) * nb[k];
+        if (brand) {
+            gu[o] = base + (cb * bpb[k] + (-cb) * bnb[k]);
+            gbp[o] = cb * ub[k];
+            gbn[o] = (-cb) * ub[k];
+        } else {
+            gu[o] = base;
+            gbp[o] = gbn[o] = 0.f;
+        }
+        gp[o] = c * ub[k];
+        gn[o] = (-c) * ub[k];
+        gu0[o] = r * ub0[k];
+        gp0[o] = r * pb0[k];
+        gn0[o] = r * nb0[k];
+    }
+    if (lane == 0) {
+        terms[b] = logf(s + 1e-8f);
+        terms[B + b] = sq;
+        terms[2 * (int64_t)B + b] = lb;
+        if (coef != nullptr) {
+            coef[b] = c;
+            coef[B + b] = cb;
+        }
+    }
+}
+
+// loss = (-(sl / B) + w * -(sb / B)) + lambda * sr / B: torch's (bpr + w * brand) + reg, the three
+// sums in k_bpr_reduce's fixed order
+static __global__ __launch_bounds__(256) void k_bpr_brand_reduce(const float* __restrict__ terms,
+                                                                 int32_t B, float lambda, float w,
+                                                                 float* __restrict__ loss) {
+    __shared__ float sl[256], sr[256], sb[256];
+    float a = 0.f, q = 0.f, t = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        a += terms[i];
+        q += terms[B + i];
+        t += terms[2 * (int64_t)B + i];
+    }
+    sl[threadIdx.x] = a;
+    sr[threadIdx.x] = q;
+    sb[threadIdx.x] = t;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            sl[threadIdx.x] += sl[threadIdx.x + h];
+            sr[threadIdx.x] += sr[threadIdx.x + h];
+            sb[threadIdx.x] += sb[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        loss[0] = (-(sl[0] / (float)B) + w * -(sb[0] / (float)B)) + lambda * sr[0] / (float)B;
+}
+
+template <typename Rows>
+inline int launch_brand(const Rows& rows, int32_t B, int32_t d, float lambda, float w,
+                        float* terms, float* loss, float* grads, float* coef, hipStream_t s) {
+    const int64_t grid = ((int64_t)B + kRowsPerBlock - 1) / kRowsPerBlock;
+    hipLaunchKernelGGL(k_bpr_brand_rows<Rows>, dim3((uint32_t)grid),
+                       dim3(kWave * kRowsPerBlock), 0, s, rows, B, d, lambda, w, terms, grads,
+                       coef);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_bpr_brand_reduce, dim3(1), dim3(256), 0, s, terms, B, lambda, w, loss);
     e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

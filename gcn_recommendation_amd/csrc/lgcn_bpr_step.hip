@@ -2,6 +2,8 @@
 // (main.py:495-525 without autograd's six gathers and six dense IndexBackward blocks):
 //   lgcn_bpr_loss_indexed  the BPR + L2 loss of lgcn_bpr_loss, rows read from the tables by index
 //   lgcn_bpr_keys          the 3B destination keys of a batch's per-sample gradient rows
+//   lgcn_bpr_brand_loss_indexed / lgcn_bpr_brand_keys   both with the brand-preference term: the
+//                          brand rows found through a device-resident item -> brand map, 5B keys
 //   lgcn_rows_scatter      deterministic scatter-accumulate of per-sample rows into table rows
 //   lgcn_rows_clear        zero exactly the rows (and mask words) a scatter touched
 // Declared in include/lgcn.h.
@@ -37,6 +39,31 @@ __global__ __launch_bounds__(256) void k_bpr_keys(const int64_t* __restrict__ us
     keys[b] = ok ? 2 * iu : none;
     keys[(int64_t)B + b] = ok ? 2 * (n_users + ip) : none;
     keys[2 * (int64_t)B + b] = ok ? 2 * (n_users + in) + 1 : none;
+}
+
+// The 5B keys of a batch with the brand term: k_bpr_keys' three, then the positive and the
+// negative item's brand row (U + I + brand). A sample without a brand keeps its first three.
+__global__ __launch_bounds__(256) void k_bpr_brand_keys(
+    const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+    const int64_t* __restrict__ neg, const int32_t* __restrict__ item_brand, int32_t B,
+    int64_t n_users, int64_t n_items, int64_t n_brands, int64_t* __restrict__ keys) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int64_t iu = users[b], ip = pos[b], in = neg[b];
+    const bool ok = iu >= 0 && iu < n_users && ip >= 0 && ip < n_items && in >= 0 && in < n_items;
+    const int64_t first = n_users + n_items;
+    const int64_t none = 2 * (first + n_brands);  // the key past every row
+    int64_t rp = -1, rn = -1;
+    if (ok) {
+        rp = item_brand[ip];
+        rn = item_brand[in];
+    }
+    const bool brand = ok && rp >= 0 && rp < n_brands && rn >= 0 && rn < n_brands;
+    keys[b] = ok ? 2 * iu : none;
+    keys[(int64_t)B + b] = ok ? 2 * (n_users + ip) : none;
+    keys[2 * (int64_t)B + b] = ok ? 2 * (n_users + in) + 1 : none;
+    keys[3 * (int64_t)B + b] = brand ? 2 * (first + rp) : none;
+    keys[4 * (int64_t)B + b] = brand ? 2 * (first + rn) + 1 : none;
 }
 
 // One wave per sorted position; the wave at the head of a run of equal rows (key >> 1) walks the
@@ -130,6 +157,41 @@ int lgcn_bpr_keys(const int64_t* users, const int64_t* pos, const int64_t* neg, 
     hipLaunchKernelGGL(k_bpr_keys, dim3((uint32_t)(((int64_t)B + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), users, pos, neg, B, n_users, n_items,
                        keys);
+    return last_err();
+}
+
+int lgcn_bpr_brand_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                                const float* fb, int64_t ld_fb, const float* u0, int64_t ld_u0,
+                                const float* i0, int64_t ld_i0, int64_t n_users, int64_t n_items,
+                                int64_t n_brands, const int64_t* users, const int64_t* pos,
+                                const int64_t* neg, const int32_t* item_brand, int32_t B,
+                                int32_t d, float lambda, float brand_weight, float* terms,
+                                float* loss, float* grads, float* coef, void* stream) {
+    if (B < 1 || d < 1 || !loss || !terms || !grads) return LGCN_EINVAL;
+    if (!fu || !fi || !fb || !u0 || !i0 || !users || !pos || !neg || !item_brand)
+        return LGCN_EINVAL;
+    if (ld_fu < d || ld_fi < d || ld_fb < d || ld_u0 < d || ld_i0 < d) return LGCN_EINVAL;
+    if (n_users < 0 || n_items < 0 || n_brands < 0) return LGCN_EINVAL;
+    const lgcn_bpr::IndexedBrandRows rows = {
+        {{fu, fi, u0, i0}, {ld_fu, ld_fi, ld_u0, ld_i0}, users, pos, neg, n_users, n_items},
+        fb, ld_fb, item_brand, n_brands};
+    return lgcn_bpr::launch_brand(rows, B, d, lambda, brand_weight, terms, loss, grads, coef,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int lgcn_bpr_brand_keys(const int64_t* users, const int64_t* pos, const int64_t* neg,
+                        const int32_t* item_brand, int32_t B, int64_t n_users, int64_t n_items,
+                        int64_t n_brands, int64_t* keys, void* stream) {
+    if (B < 1 || !users || !pos || !neg || !item_brand || !keys) return LGCN_EINVAL;
+    if (n_users < 0 || n_items < 0 || n_brands < 0) return LGCN_EINVAL;
+    // every key, the "none" one included, must fit the sort's int32 keys (each term is checked on
+    // its own first: the sum of three int64 must not wrap)
+    if (n_users > 0x3ffffffeLL || n_items > 0x3ffffffeLL || n_brands > 0x3ffffffeLL ||
+        n_users + n_items + n_brands > 0x3ffffffeLL)
+        return LGCN_EINVAL;
+    hipLaunchKernelGGL(k_bpr_brand_keys, dim3((uint32_t)(((int64_t)B + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), users, pos, neg, item_brand, B,
+                       n_users, n_items, n_brands, keys);
     return last_err();
 }
 

@@ -58,6 +58,33 @@ def load_preprocessed_data(data_dir, device, use_brand=True, debug=False, verbos
     return train_df, val_df, test_df, U, I, B, adj, item_brand_df
 
 
+def item_brand_map(item_idx, brand_idx=None, num_items=None, device=None, num_brands=None):
+    """The item -> brand map of the brand loss (main.py:504-511's item_to_brand dict) as one int32
+    [num_items] tensor for train.bpr_step(item_brand=...): -1 = the item has no brand; an item
+    listed twice keeps its last entry (dict(zip(...)), as evaluate.Evaluator reads the same
+    table). item_idx may be the item_brand_df of load_preprocessed_data (any mapping with
+    "item_idx" and "brand_idx" columns), brand_idx then None. An item index outside
+    [0, num_items) or a brand index below 0 (or, with num_brands given, >= num_brands) raises
+    ValueError."""
+    if brand_idx is None:
+        item_idx, brand_idx = item_idx["item_idx"], item_idx["brand_idx"]
+    if num_items is None:
+        raise ValueError("item_brand_map: num_items is required")
+    items = np.asarray(item_idx).astype(np.int64, copy=False).reshape(-1)
+    brands = np.asarray(brand_idx).astype(np.int64, copy=False).reshape(-1)
+    if items.shape != brands.shape:
+        raise ValueError("item_brand_map: item_idx and brand_idx differ in length")
+    if items.size and (items.min() < 0 or items.max() >= num_items):
+        raise ValueError(f"item_brand_map: an item index outside [0, {num_items})")
+    hi = 2 ** 31 if num_brands is None else num_brands
+    if brands.size and (brands.min() < 0 or brands.max() >= hi):
+        raise ValueError(f"item_brand_map: a brand index outside [0, {hi})")
+    out = np.full(int(num_items), -1, dtype=np.int32)
+    out[items] = brands  # numpy assigns repeated indices in order: the last entry stays
+    t = torch.from_numpy(out)
+    return t if device is None else t.to(device)
+
+
 def load_item_embeddings(data_dir):
     """item_embeddings.npy (amazon_books_emb/prepare_data.py:141-150) without unpickling."""
     return np.load(os.path.join(data_dir, "item_embeddings.npy"), allow_pickle=False)

@@ -191,6 +191,13 @@ ABI = [
                                              _P, _P, _P, _I32, _I32, ctypes.c_float, _P, _P, _P,
                                              _P]),
     ("lgcn_bpr_keys", ctypes.c_int, [_P, _P, _P, _I32, _I64, _I64, _P, _P]),
+    ("lgcn_bpr_brand_loss", ctypes.c_int, [_P, _I64] * 8 + [_P, _I32, _I32, ctypes.c_float,
+                                                            ctypes.c_float, _P, _P, _P, _P, _P]),
+    ("lgcn_bpr_brand_loss_indexed", ctypes.c_int, [_P, _I64] * 5 + [_I64, _I64, _I64, _P, _P, _P,
+                                                                    _P, _I32, _I32, ctypes.c_float,
+                                                                    ctypes.c_float, _P, _P, _P, _P,
+                                                                    _P]),
+    ("lgcn_bpr_brand_keys", ctypes.c_int, [_P, _P, _P, _P, _I32, _I64, _I64, _I64, _P, _P]),
     ("lgcn_rows_scatter", ctypes.c_int, [_P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64, _I32, _I32,
                                          _P, _P, _P]),
     ("lgcn_rows_clear", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),

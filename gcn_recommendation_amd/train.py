@@ -17,7 +17,13 @@ the indices in hand:
 Loss and every parameter gradient are bitwise those of main.py's route: the scatter sums each
 destination row in autograd's order (per row from +0 in ascending batch position, an item row's
 positive run plus its negative run). Nothing is read back to the host and everything is issued on
-the caller's current stream. The brand-loss branch of bpr_loss_reg is not part of this entry point.
+the caller's current stream.
+
+With `item_brand` (data.item_brand_map) the reference's optional brand loss (main.py --brand_loss)
+joins the same step: a sample has eight rows, the brand rows read from the output buffer's brand
+block through the device-resident map (lgcn_bpr_brand_loss_indexed), the batch 5B keys
+(lgcn_bpr_brand_keys) and the STORE scatter covers the brand rows of the workspace. Bitwise the
+gathered route through loss.bpr_brand_loss_reg.
 
 `bpr_epoch` is the loop around it (main.py:488-531): the batches are views of one device-side draw
 of sampler.BprSampler, the per-batch losses come back as one device tensor.
@@ -189,6 +195,116 @@ class BprStepFunction(torch.autograd.Function):
         return (None,) * 8 + blocks + ((gi,) if n_e0 == 1 else ())
 
 
+class BprBrandStepFunction(torch.autograd.Function):
+    """(graph, K, hub_threshold, lambda_reg, brand_loss_weight, users, pos, neg, item_brand, n_e0,
+    *segments) -> the loss with the brand-preference term (main.py:382-391, 499-522).
+
+    BprStepFunction with eight rows per sample: the brand rows are read from the output buffer's
+    brand block through item_brand (lgcn_bpr_brand_loss_indexed), the batch has 5B destination
+    keys (lgcn_bpr_brand_keys) and the STORE scatter of the five final-row blocks covers the
+    brand rows of the workspace too. The brand segment is required."""
+
+    @staticmethod
+    def forward(ctx, graph, K, hub_threshold, lambda_reg, brand_loss_weight, users, pos, neg,
+                item_brand, n_e0, *segments):
+        if n_e0 not in (1, 2):
+            raise engine.LgcnError(f"bpr_step: n_e0={n_e0} (1 or 2)")
+        nseg = len(segments) - (2 - n_e0)
+        if nseg != 3 or int(segments[2].shape[0]) < 1:
+            raise engine.LgcnError("bpr_step: the brand loss needs user, item and brand segments")
+        lib = engine.load_library()
+        dev = graph.device
+        segs = [t.detach() for t in segments[:nseg]]
+        sizes = [int(t.shape[0]) for t in segs]
+        U, I, NB = sizes
+        out = engine.propagate_forward(graph, segs, K, hub_threshold)
+        d = int(out.shape[1])
+        i0 = segs[1] if n_e0 == 2 else segments[nseg].detach()
+        if i0.shape != (I, d) or i0.dtype != torch.float32 or i0.device != dev or \
+                (I > 0 and i0.stride(1) != 1):
+            raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
+        B = int(users.shape[0])
+        fu, fi, fb, u0 = out[:U], out[U:U + I], out[U + I:U + I + NB], segs[0]
+        terms = torch.empty(3 * B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((8, B, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_bpr_brand_loss_indexed(
+                engine._ptr(fu), d, engine._ptr(fi), d, engine._ptr(fb), d, engine._ptr(u0), d,
+                engine._ptr(i0), i0.stride(0) if I else d, U, I, NB, engine._ptr(users),
+                engine._ptr(pos), engine._ptr(neg), engine._ptr(item_brand), B, d,
+                float(lambda_reg), float(brand_loss_weight), engine._ptr(terms),
+                engine._ptr(loss), engine._ptr(grads), None, engine._stream(dev)),
+                "lgcn_bpr_brand_loss_indexed")
+        ctx.save_for_backward(grads, users, pos, neg, item_brand)
+        ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
+        ctx.sizes, ctx.n_e0 = sizes, n_e0
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads, users, pos, neg, item_brand = ctx.saved_tensors
+        graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
+        U, I, NB = sizes
+        n = U + I + NB
+        _, B, d = grads.shape
+        m = 5 * B
+        lib = engine.load_library()
+        dev = graph.device
+        # the layer-0 blocks [3B x d], then the final-row blocks [5B x d] (include/lgcn.h): a
+        # permutation entry of the 5B keys stays inside sg whichever source it indexes
+        sg = (grads * g).view(8 * B, d)
+        ws = _workspace(graph, d)
+        gi = None
+        with torch.cuda.device(dev):
+            stream = engine._stream(dev)
+            if ws.dirty:
+                ws.rezero()
+            n_keys = 2 * n + 1
+            ws.sort_scratch(lib, m, n_keys, stream)
+            engine._check(lib.lgcn_bpr_brand_keys(engine._ptr(users), engine._ptr(pos),
+                                                  engine._ptr(neg), engine._ptr(item_brand), B, U,
+                                                  I, NB, engine._ptr(ws.keys), stream),
+                          "lgcn_bpr_brand_keys")
+            b = ws.i32
+            nbytes = ctypes.c_size_t(ws.temp_bytes)
+            engine._check(lib.lgcn_coo_sort_perm(engine._ptr(ws.keys), m, n_keys, engine._ptr(b[0]),
+                                                 engine._ptr(b[1]), engine._ptr(b[2]),
+                                                 engine._ptr(b[3]), engine._ptr(ws.temp),
+                                                 ctypes.byref(nbytes), stream),
+                          "lgcn_coo_sort_perm")
+            ws.dirty = True
+            _scatter(lib, ws, m, sg[3 * B:], 0, n, ws.G, engine.LGCN_SCATTER_STORE, ws.mask,
+                     ws.count, stream)
+            g0 = engine.propagate_backward(graph, ws.G, ctx.K, ctx.hub_threshold,
+                                           nz=(ws.mask, ws.count))
+            _scatter(lib, ws, m, sg, 0, U + I if n_e0 == 2 else U, g0,
+                     engine.LGCN_SCATTER_ADD, None, None, stream)
+            if n_e0 == 1:
+                gi = torch.zeros((I, d), dtype=torch.float32, device=dev)
+                _scatter(lib, ws, m, sg, U, U + I, gi, engine.LGCN_SCATTER_STORE, None, None,
+                         stream)
+            engine._check(lib.lgcn_rows_clear(engine._ptr(b[1]), m, 0, n, engine._ptr(ws.G), d,
+                                              d, engine._ptr(ws.mask), engine._ptr(ws.count),
+                                              stream), "lgcn_rows_clear")
+            ws.dirty = False
+        blocks = tuple(torch.split(g0, sizes, 0))
+        return (None,) * 10 + blocks + ((gi,) if n_e0 == 1 else ())
+
+
+def _check_item_brand(item_brand, num_items, device):
+    if not torch.is_tensor(item_brand) or item_brand.dtype != torch.int32:
+        raise engine.LgcnError("bpr_step: item_brand must be an int32 tensor (data.item_brand_map),"
+                               f" got {getattr(item_brand, 'dtype', type(item_brand))}")
+    if item_brand.dim() != 1 or int(item_brand.shape[0]) != num_items or \
+            not item_brand.is_contiguous():
+        raise engine.LgcnError(f"bpr_step: item_brand must be a contiguous 1-D tensor of "
+                               f"{num_items} entries, got {tuple(item_brand.shape)}")
+    if item_brand.device != device:
+        raise engine.LgcnError(f"bpr_step: item_brand on {item_brand.device}, adjacency on "
+                               f"{device}")
+
+
 def _check_index_tensors(users, pos, neg, device):
     B = None
     for name, t in (("users", users), ("pos", pos), ("neg", neg)):
@@ -207,8 +323,9 @@ def _check_index_tensors(users, pos, neg, device):
         raise engine.LgcnError("bpr_step: empty batch")
 
 
-def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False):
-    """The loss of one BPR batch (main.py:495-522 with brand_loss off) as a tensor whose
+def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, item_brand=None,
+             brand_loss_weight=0.1):
+    """The loss of one BPR batch (main.py:495-522) as a tensor whose
     `.backward()` leaves exactly the parameter `.grad`s main.py's route leaves:
 
         optimizer.zero_grad()
@@ -220,18 +337,39 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False):
     sizes with torch ops first (one sync) and raises LgcnError; by default nothing is checked or
     synchronised — the kernels are memory-safe either way (a sample with an index outside its
     table is skipped). On a CPU adjacency the reference's own expression runs (model(adj), the
-    gathers, the torch formula): the device dispatch of the models and loss.py. The brand-loss
-    branch of bpr_loss_reg is not part of this entry point."""
+    gathers, the torch formula): the device dispatch of the models and loss.py.
+
+    item_brand (data.item_brand_map: a contiguous int32 [num_items] tensor on the adjacency's
+    device, -1 = no brand; anything else raises LgcnError before any launch) switches the
+    reference's brand loss on (main.py --brand_loss): the loss is `bpr + brand_loss_weight *
+    brand + reg`, the brand rows of a sample are looked up on the device, and loss and `.grad`s
+    are bitwise those of the gathered route through loss.bpr_brand_loss_reg. A sample whose
+    positive or negative item has no brand contributes no brand term (the mean still divides by
+    the batch size). item_brand=None or brand_loss_weight == 0 is the step without the term. On a
+    CPU adjacency bpr_loss_reg(brand_loss=True, ...) runs; an unbranded item in the batch raises
+    LgcnError there, where the reference's indexing would take -1 for the last brand."""
     _check_index_tensors(users, pos, neg, adj.device)
     U, I = model.num_users, model.num_items
+    brand = item_brand is not None and brand_loss_weight != 0
+    if brand:
+        _check_item_brand(item_brand, I, adj.device)
     if check_indices:
         for name, t, n in (("users", users, U), ("pos", pos, I), ("neg", neg, I)):
             if bool(((t < 0) | (t >= n)).any()):
                 raise engine.LgcnError(f"bpr_step: {name} holds an index outside [0, {n})")
     if adj.device.type != "cuda":
         fu, fi, fb, u0, i0 = model(adj)
+        if not brand:
+            return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg],
+                                lambda_reg, final_brand_emb=fb)
+        pb, nb = item_brand[pos].long(), item_brand[neg].long()
+        n_brands = int(fb.shape[0])
+        if bool(((pb < 0) | (pb >= n_brands) | (nb < 0) | (nb >= n_brands)).any()):
+            raise engine.LgcnError("bpr_step: an item of the batch has no brand; the CPU route "
+                                   "cannot leave the sample out of the brand term")
         return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg], lambda_reg,
-                            final_brand_emb=fb)
+                            brand_loss=True, final_brand_emb=fb, pos_item_brand_idx=pb,
+                            neg_item_brand_idx=nb, brand_loss_weight=brand_loss_weight)
     n_e0 = model._bpr_n_e0
     if n_e0 == 2:
         tensors = [model.user_embedding.weight, model.item_embedding.weight,
@@ -240,11 +378,16 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False):
         tensors = [model.user_embedding.weight, model.fused_item_embedding(),
                    model.brand_embedding.weight, model.item_id_embedding.weight]
     graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
+    if brand:
+        return BprBrandStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                          float(lambda_reg), float(brand_loss_weight), users, pos,
+                                          neg, item_brand, n_e0, *tensors)
     return BprStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
                                  float(lambda_reg), users, pos, neg, n_e0, *tensors)
 
 
-def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True):
+def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
+              item_brand=None, brand_loss_weight=0.1):
     """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
     epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
     batch
@@ -256,7 +399,8 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     (empty for a sampler without interactions); nothing is read back inside the loop. A sample
     whose user has no free item carries neg = -1: on a HIP device bpr_step skips it
     (sampler.unsampled counts them); on a CPU adjacency, where the reference's own indexing would
-    take -1 for the last item, it raises before the first optimizer step."""
+    take -1 for the last item, it raises before the first optimizer step. item_brand and
+    brand_loss_weight are bpr_step's: the brand loss of every batch, looked up on the device."""
     if sampler.device != adj.device:
         raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
     batches = sampler.epoch(epoch, batch_size, shuffle=shuffle)  # the draw is made here
@@ -266,7 +410,8 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     losses = []
     for users, pos, neg in batches:
         optimizer.zero_grad()
-        loss = model.bpr_step(adj, users, pos, neg, lambda_reg)
+        loss = model.bpr_step(adj, users, pos, neg, lambda_reg, item_brand=item_brand,
+                              brand_loss_weight=brand_loss_weight)
         loss.backward()
         optimizer.step()
         losses.append(loss.detach())

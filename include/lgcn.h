@@ -45,7 +45,8 @@ extern "C" {
 
 /* 14 since the sided propagation; the training-step entry points (lgcn_bpr_loss_indexed,
  * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) and the sampler (lgcn_bpr_sample,
- * LGCN_TUNE_SAMPLE_BLOCKS) and the rank evaluation (lgcn_score_rank) were added without a bump:
+ * LGCN_TUNE_SAMPLE_BLOCKS), the rank evaluation (lgcn_score_rank) and the brand-loss entry points
+ * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) were added without a bump:
  * purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
@@ -689,6 +690,57 @@ int lgcn_rows_scatter(const int32_t* keys_sorted, const int32_t* perm, int32_t n
 int lgcn_rows_clear(const int32_t* keys_sorted, int32_t n, int32_t row_lo, int32_t row_hi,
                     float* dst, int64_t ld_dst, int32_t d, uint32_t* mask, int32_t* count,
                     void* stream);
+
+/* ---- the brand-preference term of the training batch (main.py:382-391, 499-522) -------------- */
+/* lgcn_bpr_loss plus the reference's optional second BPR term over the final brand rows bp / bn of
+ * a sample's positive / negative item, w = brand_weight:
+ *   *loss = (bpr + w * -mean_b log(sigmoid(<u_b,bp_b> - <u_b,bn_b>) + 1e-8)) + reg
+ * with bpr and reg lgcn_bpr_loss's two terms, each sum in its fixed order and
+ *   *loss = fp32(fp32(-(sl/B)) + fp32(w * fp32(-(sb/B)))) + fp32(fp32(lambda * sr) / B).
+ * Per sample x' = <u,bp> - <u,bn> (the fma and wave-sum order of the base scores),
+ * s' = 1 / (1 + expf(-x')), c' = ((-w/B) / (s' + 1e-8f)) * (1 - s') * s', and
+ *   du  = fp32(fp32(c*p) + fp32(-c*n)) + fp32(fp32(c'*bp) + fp32(-c'*bn)),
+ *   dbp = c'*u, dbn = (-c')*u; dp, dn and the layer-0 rows as lgcn_bpr_loss writes them.
+ * grads = [8 x B x d] in the order u0, p0, n0, u, p, n, bp, bn: blocks [3, 8) are one [5B x d]
+ * source for lgcn_rows_scatter under lgcn_bpr_brand_keys' 5B keys, blocks [0, 3) the layer-0
+ * source under the same keys (a permutation entry of a brand key, >= 3B, stays inside grads).
+ * terms: scratch [3 x B] (log term, squared norms, brand log term logf(s' + 1e-8f)).
+ * coef (NULL = not wanted): [2 x B], (c_b, c'_b).
+ * brand_ok (NULL = every sample): uint8 [B]; a sample with brand_ok[b] == 0 has no brand term —
+ * c' = 0, a zero brand log term, +0 dbp / dbn rows, and du exactly lgcn_bpr_loss's; rows b of bp
+ * and bn are not read. The means still divide by B. */
+int lgcn_bpr_brand_loss(const float* u, int64_t ldu, const float* p, int64_t ldp, const float* n,
+                        int64_t ldn, const float* u0, int64_t ldu0, const float* p0, int64_t ldp0,
+                        const float* n0, int64_t ldn0, const float* bp, int64_t ldbp,
+                        const float* bn, int64_t ldbn, const uint8_t* brand_ok, int32_t B,
+                        int32_t d, float lambda, float brand_weight, float* terms, float* loss,
+                        float* grads, float* coef, void* stream);
+
+/* lgcn_bpr_brand_loss with the rows read from the tables (lgcn_bpr_loss_indexed's, plus fb, the
+ * final brand table [n_brands x ld_fb]): bp = fb + item_brand[pos[b]] * ld_fb, bn likewise from
+ * neg[b]; item_brand: device int32 [n_items]. A sample whose positive or negative item maps
+ * outside [0, n_brands) (-1 = the item has no brand) has no brand term, as under brand_ok == 0. A
+ * sample with a user or item index outside its table is skipped whole: zero terms, coefficients
+ * and gradient rows, item_brand not read. Same kernels as lgcn_bpr_brand_loss: bitwise its
+ * outputs on gathered copies. */
+int lgcn_bpr_brand_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                                const float* fb, int64_t ld_fb, const float* u0, int64_t ld_u0,
+                                const float* i0, int64_t ld_i0, int64_t n_users, int64_t n_items,
+                                int64_t n_brands, const int64_t* users, const int64_t* pos,
+                                const int64_t* neg, const int32_t* item_brand, int32_t B,
+                                int32_t d, float lambda, float brand_weight, float* terms,
+                                float* loss, float* grads, float* coef, void* stream);
+
+/* The 5B destination keys of that batch's final-row gradient blocks, keys [5 x B] int64:
+ * lgcn_bpr_keys' 3B, then [3B,4B) the positive item's brand row (bit 0 clear) and [4B,5B) the
+ * negative item's (bit 0 set), brand r -> row n_users + n_items + r. "None" =
+ * 2 * (n_users + n_items + n_brands), past every row: all five keys of a skipped sample, the two
+ * brand keys of a sample without a brand term. Sort with n_keys = none + 1. LGCN_EINVAL when that
+ * would not fit the sort's int32 keys (n_users + n_items + n_brands > 0x3ffffffe). A brand row is
+ * then summed like an item row: (+0 + its positive run) + (+0 + its negative run). */
+int lgcn_bpr_brand_keys(const int64_t* users, const int64_t* pos, const int64_t* neg,
+                        const int32_t* item_brand, int32_t B, int64_t n_users, int64_t n_items,
+                        int64_t n_brands, int64_t* keys, void* stream);
 
 /* ---- BPR negative sampler (main.py:349-363, BPRDataset.__getitem__) -------------------------- */
 /* The triples of `count` training samples in one launch (count may be a whole epoch). Output slot

@@ -11,9 +11,17 @@ bpr_loss_reg, backward — bench.py's bench_train_step) and the fused model.bpr_
   * whole steps (batch to device ... loss.item(), as main.py:488-531) with Adam's default
     (foreach) and fused=True, alternating blocks, median over the blocks.
 
+--brand-loss times the brand-preference term (main.py --brand_loss) at the same shapes: the graph
+gets --brands brand rows without edges, every item a brand, and three routes run in alternating
+blocks — main_route_brand (model(adj), six gathers, bpr_loss_reg(brand_loss=True) fed by the device
+lookups item_brand[pos] / item_brand[neg]), bpr_step_brand (model.bpr_step(item_brand=...)) and
+the plain bpr_step beside them. bpr_step_brand's first batch is asserted bit-equal to the gathered
+route through loss.bpr_brand_loss_reg; against bpr_loss_reg's torch expression of the brand term
+the relative loss difference is reported.
+
 Prints one JSON line on stdout (progress goes to stderr).
 
-    python tools/bpr_step_bench.py [--config c3] [--blocks 5] [--steps-per-block 4]
+    python tools/bpr_step_bench.py [--config c3] [--blocks 5] [--steps-per-block 4] [--brand-loss]
 """
 import argparse
 import contextlib
@@ -30,21 +38,24 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (CONFIGS, make_graph, xavier: the generator bench.py times)
 from gcn_recommendation_amd import engine  # noqa: E402
-from gcn_recommendation_amd.loss import bpr_loss_reg  # noqa: E402
+from gcn_recommendation_amd.loss import bpr_brand_loss_reg, bpr_loss_reg  # noqa: E402
 from models.lightgcn import LightGCN  # noqa: E402
 
 LAMBDA = 1e-4
 
 
-def make_model(emb_host, U, I, d, K, dev):
-    """bench_train_step's construction: the drop-in LightGCN over the bench's tables, no brands."""
+def make_model(emb_host, U, I, d, K, dev, brands=None):
+    """bench_train_step's construction: the drop-in LightGCN over the bench's tables, no brands
+    (or the [n_brands x d] table `brands`)."""
     with contextlib.redirect_stdout(io.StringIO()):
         model = LightGCN.__new__(LightGCN)
         torch.nn.Module.__init__(model)
-        model.num_users, model.num_items, model.num_brands = U, I, 0
+        model.num_users, model.num_items = U, I
+        model.num_brands = 0 if brands is None else int(brands.shape[0])
         model.embedding_dim, model.n_layers, model.debug = d, K, False
         model.user_embedding = torch.nn.Embedding.from_pretrained(emb_host[0].clone(), freeze=False)
-        model.brand_embedding = torch.nn.Embedding(0, d)
+        model.brand_embedding = torch.nn.Embedding(0, d) if brands is None else \
+            torch.nn.Embedding.from_pretrained(brands.clone(), freeze=False)
         model.item_embedding = torch.nn.Embedding.from_pretrained(emb_host[1].clone(), freeze=False)
         model.final_brand_emb, model._graph_adj = None, None
     return model.to(dev)
@@ -77,6 +88,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--steps-per-block", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--brand-loss", action="store_true",
+                    help="time the brand-preference term: main_route_brand, bpr_step_brand and "
+                         "the plain bpr_step in one run")
+    ap.add_argument("--brands", type=int, default=4096, help="brand rows of --brand-loss")
+    ap.add_argument("--brand-loss-weight", type=float, default=0.1)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bpr_step_bench: needs a HIP device")
@@ -88,12 +104,38 @@ def main():
     gen = torch.Generator().manual_seed(42)
     emb_host = [bench.xavier(U, d, gen), bench.xavier(I, d, gen)]
     r, c, v = bench.make_graph(dict(cfg, brands=0), args.gen, 16)[:3]
-    n = U + I
+    NB = args.brands if args.brand_loss else 0
+    n = U + I + NB  # the brand rows of --brand-loss have no edges: the graph is the same
     adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack((r, c))), torch.from_numpy(v),
                                   (n, n)).to(dev)
     nnz = len(v)
     del r, c, v
-    models = {name: make_model(emb_host, U, I, d, K, dev) for name, _ in ROUTES}
+    if args.brand_loss:
+        if NB < 1:
+            sys.exit("bpr_step_bench: --brand-loss needs --brands >= 1")
+        emb_host.append(bench.xavier(NB, d, gen))
+        item_brand = torch.from_numpy(np.random.default_rng(7).integers(0, NB, I)).to(
+            dev, torch.int32)
+        w = args.brand_loss_weight
+
+        def loss_main_brand(model, adj, users, pos, neg, reg=bpr_loss_reg):
+            fu, fi, fb, u0, i0 = model(adj, use_brand=False)
+            return reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg], LAMBDA,
+                       brand_loss=True, final_brand_emb=fb,
+                       pos_item_brand_idx=item_brand[pos].long(),
+                       neg_item_brand_idx=item_brand[neg].long(), brand_loss_weight=w)
+
+        def loss_step_brand(model, adj, users, pos, neg):
+            return model.bpr_step(adj, users, pos, neg, LAMBDA, item_brand=item_brand,
+                                  brand_loss_weight=w)
+
+        routes = (("main_route_brand", loss_main_brand), ("bpr_step_brand", loss_step_brand),
+                  ("bpr_step", loss_step))
+    else:
+        routes = ROUTES
+    REF, FUSED = routes[0][0], routes[1][0]
+    models = {name: make_model(emb_host, U, I, d, K, dev, emb_host[2] if NB else None)
+              for name, _ in routes}
     rng = np.random.default_rng(0)
     n_batches = max(args.blocks * args.steps_per_block, args.warmup) + 1
     batches = [tuple(torch.from_numpy(rng.integers(0, hi, args.batch)) for hi in (U, I, I))
@@ -102,12 +144,20 @@ def main():
     # ---- the first batch: same bits -------------------------------------------------------------
     first = tuple(t.to(dev) for t in batches[-1])
     got = {}
-    for name, fn in ROUTES:
+    for name, fn in routes:
         m = models[name]
         loss = fn(m, adj, *first)
         loss.backward()
         got[name] = (loss.detach().clone(), {k: p.grad for k, p in m.named_parameters()})
-    (l0, g0), (l1, g1) = got["main_route"], got["bpr_step"]
+    (l0, g0), (l1, g1) = got[REF], got[FUSED]
+    loss_rel_diff = None
+    if args.brand_loss:  # REF's brand term is torch's expression: bit-equal to the gathered route
+        loss_rel_diff = abs(l0.item() - l1.item()) / abs(l0.item())
+        m = make_model(emb_host, U, I, d, K, dev, emb_host[2])
+        l0 = loss_main_brand(m, adj, *first, reg=bpr_brand_loss_reg)
+        l0.backward()
+        l0, g0 = l0.detach().clone(), {k: p.grad for k, p in m.named_parameters()}
+        del m
     assert bits_equal(l0, l1), f"loss differs: {l0.item()!r} vs {l1.item()!r}"
     for k in g0:
         assert bits_equal(g0[k], g1[k]), f"gradient of {k} differs"
@@ -125,14 +175,14 @@ def main():
         return loss.item()
 
     def blocks_of_whole_steps(opts):
-        per_block = {name: [] for name, _ in ROUTES}
-        for name, fn in ROUTES:
+        per_block = {name: [] for name, _ in routes}
+        for name, fn in routes:
             for b in batches[:args.warmup]:
                 whole_step(name, fn, opts[name], b)
         a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for blk in range(args.blocks):
             bs = batches[blk * args.steps_per_block:(blk + 1) * args.steps_per_block]
-            for name, fn in ROUTES:
+            for name, fn in routes:
                 torch.cuda.synchronize()
                 a.record()
                 for b in bs:
@@ -143,11 +193,11 @@ def main():
         return per_block
 
     def blocks_of_phases(opts):
-        per_block = {name: [] for name, _ in ROUTES}
+        per_block = {name: [] for name, _ in routes}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         for blk in range(args.blocks):
             bs = batches[blk * args.steps_per_block:(blk + 1) * args.steps_per_block]
-            for name, fn in ROUTES:
+            for name, fn in routes:
                 rows = []
                 for b in bs:
                     users, pos, neg = (t.to(dev) for t in b)
@@ -168,40 +218,49 @@ def main():
     result = {"config": cfg["name"], "nnz": nnz, "d": d, "K": K, "batch": args.batch,
               "blocks": args.blocks, "steps_per_block": args.steps_per_block,
               "first_batch_bit_equal": True}
-    opts = {name: torch.optim.Adam(models[name].parameters(), lr=1e-3) for name, _ in ROUTES}
+    if args.brand_loss:
+        result.update(brands=NB, brand_loss_weight=w, loss_rel_diff_vs_torch_brand_term=loss_rel_diff)
+    opts = {name: torch.optim.Adam(models[name].parameters(), lr=1e-3) for name, _ in routes}
     whole = blocks_of_whole_steps(opts)
+    bench.log("[bpr_step_bench] whole steps (Adam default) done")
     phases = blocks_of_phases(opts)
+    bench.log("[bpr_step_bench] phases done")
     names = ("forward_and_loss", "backward", "adam")
     result["phases_ms"] = {
         name: {p: round(float(np.median(phases[name][:, i])), 3) for i, p in enumerate(names)}
-        for name, _ in ROUTES}
-    result["spread_ms"] = {p: round(float(np.ptp(phases["main_route"][:, i])), 3)
+        for name, _ in routes}
+    result["spread_ms"] = {p: round(float(np.ptp(phases[REF][:, i])), 3)
                            for i, p in enumerate(names)}
     result["phase_block_medians_ms"] = {
         name: {p: [round(float(x), 3) for x in phases[name][:, i]] for i, p in enumerate(names)}
-        for name, _ in ROUTES}
-    result["gain_ms"] = {p: round(result["phases_ms"]["main_route"][p]
-                                  - result["phases_ms"]["bpr_step"][p], 3) for p in names[:2]}
+        for name, _ in routes}
+    result["gain_ms"] = {p: round(result["phases_ms"][REF][p]
+                                  - result["phases_ms"][FUSED][p], 3) for p in names[:2]}
     result["step_ms_adam_default"] = {name: round(float(np.median(whole[name])), 3)
-                                      for name, _ in ROUTES}
+                                      for name, _ in routes}
     result["step_block_ms_adam_default"] = {name: [round(x, 3) for x in whole[name]]
-                                            for name, _ in ROUTES}
+                                            for name, _ in routes}
     del opts
     opts = {name: torch.optim.Adam(models[name].parameters(), lr=1e-3, fused=True)
-            for name, _ in ROUTES}
+            for name, _ in routes}
     whole = blocks_of_whole_steps(opts)
     result["step_ms_adam_fused"] = {name: round(float(np.median(whole[name])), 3)
-                                    for name, _ in ROUTES}
+                                    for name, _ in routes}
     result["step_block_ms_adam_fused"] = {name: [round(x, 3) for x in whole[name]]
-                                          for name, _ in ROUTES}
+                                          for name, _ in routes}
     # both models saw the same batches in the same order: still the same bits
-    pa, pb = (dict(models[name].named_parameters()) for name, _ in ROUTES)
-    result["parameters_bit_equal_after_run"] = all(bits_equal(pa[k], pb[k]) for k in pa)
+    if not args.brand_loss:
+        pa, pb = (dict(models[name].named_parameters()) for name, _ in routes)
+        result["parameters_bit_equal_after_run"] = all(bits_equal(pa[k], pb[k]) for k in pa)
     result["what"] = ("main.py:488-531 per batch on one device, main_route = model(adj) + six "
                       "gathers + bpr_loss_reg + backward, bpr_step = model.bpr_step + backward; "
                       "phases between events on the current stream (median per block of steps, "
                       "then over alternating blocks); spread_ms = max - min of main_route's block "
                       "medians; step_ms_* = whole steps incl. batch upload and loss.item()")
+    if args.brand_loss:
+        result["what"] += ("; --brand-loss: main_route_brand = the same with bpr_loss_reg("
+                           "brand_loss=True) on device lookups item_brand[pos], bpr_step_brand = "
+                           "model.bpr_step(item_brand=...), brand rows without edges")
     print(json.dumps(result), flush=True)
 
 
