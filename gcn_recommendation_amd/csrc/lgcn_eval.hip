@@ -17,8 +17,10 @@
 //  * k_topk_merge: per user, the splits' K-th scores bound the global K-th from below, so only
 //    candidates >= max_s kth_s are ranked.
 //
-// lgcn_score_rank (further down) ranks one held-out item per user under the same total order. Both
-// entry points stand on the same pieces, each written once: load_row_half (guarded row load),
+// lgcn_score_rank (further down) ranks one held-out item per user under the same total order, and
+// lgcn_score_rank_lists (after it) every item of a held-out list per user from one pass over the
+// user's score row: a histogram over p(x), the number of the list's targets an item does not beat.
+// The entry points stand on the same pieces, each written once: load_row_half (guarded row load),
 // score_tile (the one MFMA chain: every score either entry point compares comes from it), c_row
 // (which user row a C register holds), and on the host eval_args, eval_split_len, user_tiles and
 // with_width. The double-buffered loop over an item split stays written out in k_score_topk and
@@ -432,6 +434,286 @@ __global__ __launch_bounds__(64) void k_rank_finish(
     if (lane == 0) rank[slot] = c;
 }
 
+// ---------------------------------------------------------------------------------------------
+// lgcn_score_rank_lists: the ranks of all the held-out items of a slot's list from ONE pass over
+// the slot's score row. Sort the list's targets under the total order, t_0 > t_1 > ... > t_{T-1}
+// (ties of (score, item), a target listed twice, by entry index). An item x beats exactly the
+// suffix {t_j : j >= p(x)}, p(x) = #{j : x does not beat t_j} (x itself among them), so a
+// histogram hist[p] over the items gives every rank: rank(t_j) = sum_{p <= j} hist[p]. The counts
+// are integers: no order of the atomics changes them.
+//  1. k_lists_target: one wave per slot, the gathered tile of k_rank_finish (every row the slot's
+//     user, column c the c-th target of the list) -> target_score; rank -1 for a target outside.
+//  2. k_lists_sort: one wave per slot places the list's entries by rank counting -> sorted
+//     (score, item, entry) and the number of ranked entries in scratch.
+//  3. k_lists_count: k_rank_count's tile loop. Per C-row the worst target of the list sits where
+//     k_rank_count keeps its one target: a score that does not beat it costs that one compare.
+//     One that does is placed by binary search in the sorted list (LDS) and counted in hist[p]
+//     (LDS, integer atomic) -> part[split][sorted place]. kListCap sorted places per slot fit
+//     one pass; a wave whose longest list is longer streams its split once per kListCap places
+//     (a chunk of the sorted list is ranked on its own: a rank depends on its own target only).
+//  4. k_lists_finish: one wave per slot sums the splits, a prefix sum per chunk gives the raw
+//     ranks, the train items' correction is k_rank_finish's with the same p(.): for each train
+//     item, out where its raw score was counted, in where -1e10 is.
+// kListCap = 32: per block 128 slots x 32 places x (score, item, count) = 48 KB of LDS, the most
+// that still lets three blocks share a CU's 160 KB, which is k_rank_count's occupancy at d <= 64
+// (64 places would leave one block per CU).
+// ---------------------------------------------------------------------------------------------
+constexpr int kListCap = 32;
+static_assert(kListCap == kUsersPerWave, "a chunk is one lane half: loads, write-out and the scan");
+
+// The first j in [0, n) whose target (ts[j], tg[j]) the item (s, x) beats; n when it beats none.
+// The lists are sorted best first, so the answer is p(x).
+__device__ __forceinline__ int list_place(const float* ts, const int32_t* tg, int n, float s,
+                                          int32_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (better(s, x, ts[mid], tg[mid])) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// The slot's entries [lo, hi) of the window that starts at trow[0]; false when they do not lie
+// inside the cap_n entries the scratch was sized for (such a slot is left alone).
+__device__ __forceinline__ bool list_range(const int32_t* __restrict__ trow, int32_t slot,
+                                           int64_t cap_n, int32_t& lo, int32_t& hi,
+                                           int32_t& base) {
+    base = trow[0];
+    lo = trow[slot];
+    hi = trow[slot + 1];
+    return lo >= base && hi >= lo && (int64_t)hi - base <= cap_n;
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void k_lists_target(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    const int32_t* __restrict__ mrow, const int32_t* __restrict__ mitems,
+    const int32_t* __restrict__ trow, const int32_t* __restrict__ titems, int64_t cap_n,
+    float* __restrict__ target_score, int32_t* __restrict__ rank) {
+    constexpr int DH = D / 2;
+    const int32_t slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    int32_t lo, hi, base;
+    if (!list_range(trow, slot, cap_n, lo, hi, base) || lo == hi) return;  // (uniform)
+    const int32_t u = users[slot];
+    const int32_t mlo = mrow[u], mhi = mrow[u + 1];
+    float4 a[D / 8], b[D / 8];
+    load_row_half<D>(uemb + (int64_t)u * ld_u + h * DH, true, a);  // every row: this user
+    for (int32_t e0 = lo; e0 < hi; e0 += 32) {
+        const int32_t e = e0 + col;
+        const int32_t t = e < hi ? titems[e] : -1;
+        const bool tok = t >= 0 && t < n_items;
+        load_row_half<D>(iemb + (tok ? (int64_t)t * ld_i : 0) + h * DH, tok, b);
+        const f32x16 acc = score_tile<D>(a, b);
+        if (h == 0 && e < hi) {
+            float sc = acc[0];
+            if (!tok) {
+                sc = __builtin_nanf("");
+                rank[e] = -1;
+            } else if (in_sorted(mitems, mlo, mhi, t)) {
+                sc = kMasked;
+            }
+            target_score[e] = sc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_lists_sort(
+    const int32_t* __restrict__ trow, const int32_t* __restrict__ titems, int32_t n_items,
+    const float* __restrict__ target_score, int64_t cap_n, int32_t* __restrict__ cnt,
+    float* __restrict__ sorted_s, int32_t* __restrict__ sorted_t, int32_t* __restrict__ sorted_e,
+    int32_t* __restrict__ rank) {
+    const int32_t slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    int32_t lo, hi, base;
+    if (!list_range(trow, slot, cap_n, lo, hi, base)) {  // (uniform)
+        if (lane == 0) cnt[slot] = 0;
+        return;
+    }
+    const int32_t T = hi - lo, rb = lo - base;
+    int32_t nv = 0;
+    for (int32_t i = lane; i < T; i += 64) {
+        const float s = target_score[lo + i];
+        const int32_t t = titems[lo + i];
+        const bool tok = t >= 0 && t < n_items;
+        // a score that is a NaN beats nothing and nothing beats it: rank 0, as lgcn_score_rank's
+        if (tok && s != s) rank[lo + i] = 0;
+        if (!tok || s != s) continue;
+        int32_t pos = 0;
+        for (int32_t k = 0; k < T; ++k) {
+            const float sk = target_score[lo + k];
+            const int32_t tk = titems[lo + k];
+            const bool ahead = better(sk, tk, s, t) || (sk == s && tk == t && k < i);
+            pos += (tk >= 0 && tk < n_items && ahead) ? 1 : 0;  // (a NaN sk is never ahead)
+        }
+        sorted_s[rb + pos] = s;
+        sorted_t[rb + pos] = t;
+        sorted_e[rb + pos] = lo + i;
+        ++nv;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nv += __shfl_xor(nv, off);
+    if (lane == 0) cnt[slot] = nv;
+}
+
+template <int D>
+__global__ __launch_bounds__(kWaves * 64, D <= 64 ? 3 : 1) void k_lists_count(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    int32_t n_users, const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    int32_t split_len, const int32_t* __restrict__ trow, const int32_t* __restrict__ cnt,
+    const float* __restrict__ sorted_s, const int32_t* __restrict__ sorted_t, int64_t cap_n,
+    int32_t* __restrict__ part) {
+    constexpr int DH = D / 2;
+    __shared__ float s_ts[kWaves][kUsersPerWave][kListCap];      // this chunk of the sorted lists
+    __shared__ int32_t s_tg[kWaves][kUsersPerWave][kListCap];
+    __shared__ int32_t s_hist[kWaves][kUsersPerWave][kListCap];
+    __shared__ __attribute__((aligned(16))) float s_ws[kWaves][kUsersPerWave];  // its worst target
+    __shared__ __attribute__((aligned(16))) int32_t s_wg[kWaves][kUsersPerWave];
+    __shared__ int32_t s_len[kWaves][kUsersPerWave];
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    const int32_t ub = (blockIdx.x * kWaves + wave) * kUsersPerWave;
+    const int32_t split = blockIdx.y;
+    const int32_t it0 = split * split_len;
+    const int32_t it1 = min(n_items, it0 + split_len);
+    const bool ok = ub + col < n_users;
+    // slot ub + col (both lane halves hold it): its ranked entries and where its sorted list starts
+    const int32_t my_T = ok ? cnt[ub + col] : 0;
+    const int32_t my_rb = ok ? trow[ub + col] - trow[0] : 0;
+    int32_t max_T = my_T;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) max_T = max(max_T, __shfl_xor(max_T, off));
+    float4 a[D / 8];
+    load_row_half<D>(uemb + (ok ? (int64_t)users[ub + col] * ld_u : 0) + h * DH, ok, a);
+    float4 bcur[D / 8], bnxt[D / 8];
+    auto load_tile = [&](int32_t t0, float4 (&b)[D / 8]) {
+        const int32_t item = t0 + col;
+        const bool iok = item < it1;
+        load_row_half<D>(iemb + (iok ? (int64_t)item * ld_i : 0) + h * DH, iok, b);
+    };
+    for (int32_t c0 = 0; c0 < max_T; c0 += kListCap) {  // (uniform over the wave)
+        // places [c0, c0 + kListCap) of every slot's sorted list; a slot with none left compares
+        // against NaN: it counts nothing
+#pragma unroll 1
+        for (int i = 0; i < kUsersPerWave / 2; ++i) {
+            const int row = 2 * i + h;
+            const int32_t len = min(max(__shfl(my_T, row) - c0, 0), kListCap);
+            const int32_t src = __shfl(my_rb, row) + c0 + col;
+            s_hist[wave][row][col] = 0;
+            if (col < len) {
+                s_ts[wave][row][col] = sorted_s[src];
+                s_tg[wave][row][col] = sorted_t[src];
+            }
+        }
+        if (h == 0) {
+            const int32_t len = min(max(my_T - c0, 0), kListCap);
+            s_len[wave][col] = len;
+            s_ws[wave][col] = len > 0 ? sorted_s[my_rb + c0 + len - 1] : __builtin_nanf("");
+            s_wg[wave][col] = len > 0 ? sorted_t[my_rb + c0 + len - 1] : -1;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(kLgkm0);
+        __builtin_amdgcn_wave_barrier();
+        if (it0 < it1) load_tile(it0, bcur);
+        for (int32_t t0 = it0; t0 < it1; t0 += 32) {
+            if (t0 + 32 < it1) load_tile(t0 + 32, bnxt);
+            const int32_t item = t0 + col;
+            const bool iok = item < it1;
+            const f32x16 acc = score_tile<D>(a, bcur);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {  // rows c_row(4g .. 4g+3, h) are four neighbours in LDS
+                const float4 ws = *reinterpret_cast<const float4*>(&s_ws[wave][c_row(4 * g, h)]);
+                const int4 wg = *reinterpret_cast<const int4*>(&s_wg[wave][c_row(4 * g, h)]);
+                const float wsq[4] = {ws.x, ws.y, ws.z, ws.w};
+                const int32_t wgq[4] = {wg.x, wg.y, wg.z, wg.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int r = 4 * g + q;
+                    if (iok && better(acc[r], item, wsq[q], wgq[q])) {
+                        const int row = c_row(r, h);
+                        // (it beats the last place: the search is over the places before it)
+                        const int p = list_place(s_ts[wave][row], s_tg[wave][row],
+                                                 s_len[wave][row] - 1, acc[r], item);
+                        atomicAdd(&s_hist[wave][row][p], 1);
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < D / 8; ++q) bcur[q] = bnxt[q];
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(kLgkm0);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+        for (int i = 0; i < kUsersPerWave / 2; ++i) {
+            const int row = 2 * i + h;
+            const int32_t dst = __shfl(my_rb, row) + c0 + col;
+            if (col < s_len[wave][row]) part[(int64_t)split * cap_n + dst] = s_hist[wave][row][col];
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(kLgkm0);  // every lane has read the chunk before the next
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void k_lists_finish(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    const int32_t* __restrict__ mrow, const int32_t* __restrict__ mitems,
+    const int32_t* __restrict__ trow, const int32_t* __restrict__ cnt,
+    const float* __restrict__ sorted_s, const int32_t* __restrict__ sorted_t,
+    const int32_t* __restrict__ sorted_e, int64_t cap_n, const int32_t* __restrict__ part,
+    int32_t n_splits, int32_t* __restrict__ rank) {
+    constexpr int DH = D / 2;
+    const int32_t slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    const int32_t T = cnt[slot];
+    if (T == 0) return;  // (uniform; a slot outside the scratch has no ranked entry either)
+    const int32_t rb = trow[slot] - trow[0];
+    const int32_t u = users[slot];
+    const int32_t lo = mrow[u], hi = mrow[u + 1];
+    const float* ss = sorted_s + rb;
+    const int32_t* st = sorted_t + rb;
+    float4 a[D / 8], b[D / 8];
+    if (lo < hi) load_row_half<D>(uemb + (int64_t)u * ld_u + h * DH, true, a);
+    for (int32_t j0 = 0; j0 < T; j0 += 64) {  // two chunks of the sorted list, one per lane half
+        const int32_t j = j0 + lane;
+        int32_t c = 0;
+        if (j < T)
+            for (int32_t s = 0; s < n_splits; ++s) c += part[(int64_t)s * cap_n + rb + j];
+        // hist -> rank within the chunk: an inclusive prefix sum over the lane half
+#pragma unroll
+        for (int off = 1; off < kListCap; off <<= 1) {
+            const int32_t v = __shfl_up(c, off, kListCap);
+            if (col >= off) c += v;
+        }
+        for (int32_t e0 = lo; e0 < hi; e0 += 32) {
+            const int32_t e = e0 + col;
+            const int32_t m = e < hi ? mitems[e] : -1;
+            // (an entry outside the table masks nothing; a repeated entry masks once)
+            const bool mok = m >= 0 && m < n_items && !(e > lo && mitems[e - 1] == m);
+            load_row_half<D>(iemb + (mok ? (int64_t)m * ld_i : 0) + h * DH, mok, b);
+            const f32x16 acc = score_tile<D>(a, b);
+            int32_t p_raw = INT32_MAX, p_msk = INT32_MAX;
+            if (h == 0 && mok) {
+                p_raw = list_place(ss, st, T, acc[0], m);
+                p_msk = list_place(ss, st, T, kMasked, m);
+            }
+            for (int k = 0; k < 32; ++k)  // train item k of this tile: out at p_raw, in at p_msk
+                c += (__shfl(p_msk, k) <= j ? 1 : 0) - (__shfl(p_raw, k) <= j ? 1 : 0);
+        }
+        if (j < T) rank[sorted_e[rb + j]] = c;
+    }
+}
+
 // ---- host side ----
 constexpr int64_t user_tiles(int64_t n_users) {  // blocks of kWaves x 32 user slots
     return (n_users + kWaves * kUsersPerWave - 1) / (kWaves * kUsersPerWave);
@@ -463,6 +745,12 @@ hipError_t with_width(int32_t d, F&& f) {
         case 128: return f(std::integral_constant<int, 128>{});
         default: return f(std::integral_constant<int, 256>{});
     }
+}
+
+// Scratch of lgcn_score_rank_lists for n entries: cnt [n_users] | sorted score, item, entry [n]
+// each | part [n_splits x n].
+constexpr size_t lists_bytes(int64_t n_users, int64_t n, int64_t n_splits) {
+    return ((size_t)4 * n_users + (size_t)(12 + 4 * n_splits) * n + 15) / 16 * 16;
 }
 
 }  // namespace
@@ -545,6 +833,60 @@ int lgcn_score_rank(const float* user_emb, int64_t ld_u, const int32_t* users, i
         hipLaunchKernelGGL(k_rank_finish<D>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u, users,
                            n_users, item_emb, ld_i, n_items, mask_rowptr, mask_items, targets,
                            target_score, part, n_splits, rank);
+        return hipGetLastError();
+    });
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+size_t lgcn_score_rank_lists_scratch_bytes(int32_t n_users, int64_t n_targets, int32_t n_splits) {
+    if (n_users < 0 || n_targets < 0 || n_splits < 1 || n_splits > 256) return 0;
+    return lists_bytes(n_users, n_targets, n_splits);
+}
+
+int lgcn_score_rank_lists(const float* user_emb, int64_t ld_u, const int32_t* users,
+                          int32_t n_users, const float* item_emb, int64_t ld_i,
+                          int32_t n_items, int32_t d,
+                          const int32_t* mask_rowptr, const int32_t* mask_items,
+                          const int32_t* target_rowptr, const int32_t* target_items,
+                          int32_t n_splits, void* scratch, size_t scratch_bytes,
+                          float* target_score, int32_t* rank, void* stream) {
+    if (const int rc = eval_args(user_emb, ld_u, n_users, item_emb, ld_i, n_items, d, n_splits))
+        return rc;
+    if (n_users == 0) return 0;
+    if (!user_emb || !users || !item_emb || !mask_rowptr || !target_rowptr || !target_items ||
+        !scratch || !target_score || !rank)
+        return LGCN_EINVAL;
+    if (scratch_bytes < lists_bytes(n_users, 0, n_splits)) return LGCN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(scratch) & 3) return LGCN_EALIGN;
+    // the entries the scratch holds (the host never reads target_rowptr: the kernels leave a slot
+    // whose entries lie past them alone)
+    const int64_t cap_n =
+        (int64_t)((scratch_bytes - (size_t)4 * n_users) / (size_t)(12 + 4 * n_splits));
+    int32_t* cnt = static_cast<int32_t*>(scratch);
+    float* sorted_s = reinterpret_cast<float*>(cnt + n_users);
+    int32_t* sorted_t = reinterpret_cast<int32_t*>(sorted_s + cap_n);
+    int32_t* sorted_e = sorted_t + cap_n;
+    int32_t* part = sorted_e + cap_n;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t split_len = eval_split_len(n_items, n_splits);
+    const int32_t tiles = user_tiles(n_users);
+    const hipError_t e = with_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        hipLaunchKernelGGL(k_lists_target<D>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u, users,
+                           item_emb, ld_i, n_items, mask_rowptr, mask_items, target_rowptr,
+                           target_items, cap_n, target_score, rank);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_lists_sort, dim3(n_users), dim3(64), 0, s, target_rowptr, target_items,
+                           n_items, target_score, cap_n, cnt, sorted_s, sorted_t, sorted_e, rank);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_lists_count<D>, dim3(tiles, n_splits), dim3(kWaves * 64), 0, s,
+                           user_emb, ld_u, users, n_users, item_emb, ld_i, n_items, split_len,
+                           target_rowptr, cnt, sorted_s, sorted_t, cap_n, part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_lists_finish<D>, dim3(n_users), dim3(64), 0, s, user_emb, ld_u, users,
+                           item_emb, ld_i, n_items, mask_rowptr, mask_items, target_rowptr, cnt,
+                           sorted_s, sorted_t, sorted_e, cap_n, part, n_splits, rank);
         return hipGetLastError();
     });
     return e == hipSuccess ? 0 : (int)e;

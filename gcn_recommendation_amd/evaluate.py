@@ -326,6 +326,178 @@ def metrics_from_ranks(ranks, ks=(20,)):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# list path: lgcn_score_rank_lists (several held-out items per user, one pass over the score row)
+# ----------------------------------------------------------------------------------------------
+# The usual LightGCN splits hold out many items per user. Every entry's rank is what
+# lgcn_score_rank gives for the pair on its own (the other held-out items of the user count as
+# ordinary items), so the list metrics are functions of the ranks and the lists' lengths.
+def target_csr(users, items):
+    """(eval_users int64 [n], rowptr int32 [n + 1], items int32 [rowptr[-1]]) as numpy: the
+    distinct users that occur, ascending, each with its de-duplicated, sorted item list. Every
+    row of the frame is kept (evaluate()'s dict(zip(...)) keeps a user's last). An item that no
+    int32 holds becomes -1: there is no such item, it ranks -1."""
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    items = np.asarray(items, dtype=np.int64).reshape(-1)
+    if users.shape != items.shape:
+        raise ValueError(f"target_csr: {users.size} users but {items.size} items")
+    if users.size == 0:
+        return np.zeros(0, np.int64), np.zeros(1, np.int32), np.zeros(0, np.int32)
+    if users.size >= 1 << 31:
+        raise ValueError("target_csr: the pair count must be below 2^31")
+    pairs = np.unique(np.stack([users, items], 1), axis=0)  # sorted by (user, item), distinct
+    eval_users, counts = np.unique(pairs[:, 0], return_counts=True)
+    rowptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    it = pairs[:, 1]
+    it = np.where((it < 0) | (it >= 1 << 31), -1, it).astype(np.int32)
+    return eval_users, rowptr, it
+
+
+def _list_slots(users, rowptr, items, n_table, n_items, dev):
+    """(users int32, rowptr int32, items int32) for the kernel, as _slots gives them for pairs: a
+    target outside [0, n_items) becomes -1, and so does every target of a user outside the table,
+    whose id becomes 0. Device ops only, no read-back."""
+    users = _index_tensor("users", users, dev)
+    rowptr = _index_tensor("target_rowptr", rowptr, dev)
+    items = _index_tensor("target_items", items, dev)
+    if rowptr.numel() != users.numel() + 1:
+        raise ValueError(f"rank lists: {users.numel()} users need {users.numel() + 1} offsets, "
+                         f"not {rowptr.numel()}")
+    bad_u = (users < 0) | (users >= n_table)
+    bad_t = (items < 0) | (items >= n_items)
+    if users.numel() and items.numel():
+        entry = torch.arange(items.numel(), device=dev, dtype=rowptr.dtype)
+        slot = (torch.searchsorted(rowptr, entry, right=True) - 1).clamp_(0, users.numel() - 1)
+        bad_t = bad_t | bad_u[slot]
+    users = torch.where(bad_u, torch.zeros_like(users), users).to(torch.int32)
+    items = torch.where(bad_t, torch.full_like(items, -1), items).to(torch.int32)
+    return users.contiguous(), rowptr.to(torch.int32).contiguous(), items.contiguous()
+
+
+def _rank_lists_launch(ue, ie, users, rowptr, items, mrow, mit, rank, score, scratch, n_splits):
+    """One lgcn_score_rank_lists on prepared device tensors: int32 users [n > 0], rowptr (a view
+    of n + 1 offsets into items / rank / score, which are passed whole) and a uint8 scratch, on
+    the current stream."""
+    lib = engine.load_library()
+    dev = ie.device
+    P = engine._ptr
+    with torch.cuda.device(dev):
+        engine._check(lib.lgcn_score_rank_lists(
+            P(ue), ue.stride(0), P(users), int(users.numel()), P(ie), ie.stride(0),
+            int(ie.shape[0]), int(ie.shape[1]), P(mrow), P(mit), P(rowptr), P(items), n_splits,
+            P(scratch), int(scratch.numel()), P(score), P(rank), engine._stream(dev)),
+            "lgcn_score_rank_lists")
+
+
+def _lists_scratch(n_slots, n_targets, n_splits, dev):
+    nbytes = engine.load_library().lgcn_score_rank_lists_scratch_bytes(n_slots, n_targets,
+                                                                       n_splits)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def rank_lists_fused(user_emb, item_emb, users, target_rowptr, target_items, mask_rowptr,
+                     mask_items):
+    """(ranks int32 [n_targets], target_scores fp32 [n_targets]) on the tables' HIP device:
+    lgcn_score_rank_lists. Slot b is users[b] with the entries target_rowptr[b]:target_rowptr[b+1]
+    of target_items; every entry gets what rank_fused gives the pair on its own. Entries that
+    belong to no slot keep rank -1 and a NaN score. The argument rules are rank_fused's."""
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    if dev.type != "cuda":
+        raise engine.LgcnError("rank_lists_fused needs tables on a HIP device (rank_lists_torch "
+                               "runs anywhere)")
+    if item_emb.shape[1] not in FUSED_DIMS:
+        raise engine.LgcnError(f"rank_lists_fused: d = {item_emb.shape[1]} not in {FUSED_DIMS}")
+    mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev)
+    mit = _mask_tensor("mask_items", mask_items, dev)
+    if mrow.numel() != user_emb.shape[0] + 1:
+        raise ValueError("rank: mask_rowptr must hold one entry per user row and one more")
+    users, rowptr, items = _list_slots(users, target_rowptr, target_items, user_emb.shape[0],
+                                       item_emb.shape[0], dev)
+    n, n_targets = int(users.numel()), int(items.numel())
+    rank = torch.full((n_targets,), -1, dtype=torch.int32, device=dev)
+    score = torch.full((n_targets,), float("nan"), dtype=torch.float32, device=dev)
+    if n == 0 or n_targets == 0:
+        return rank, score
+    splits = engine.load_library().lgcn_eval_splits(n, int(item_emb.shape[0]), _device_cus(dev))
+    _rank_lists_launch(_rows(user_emb), _rows(item_emb), users, rowptr, items, mrow,
+                       _items_to_pass(mit), rank, score, _lists_scratch(n, n_targets, splits, dev),
+                       splits)
+    return rank, score
+
+
+def rank_lists_torch(user_emb, item_emb, users, target_rowptr, target_items, mask_rowptr,
+                     mask_items, batch_size=1024):
+    """rank_lists_fused's result with torch ops, for any width and device (CPU included):
+    rank_torch on the (user, item) pairs the lists expand to. The offsets are read on the host."""
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    users = _index_tensor("users", users, dev)
+    items = _index_tensor("target_items", target_items, dev)
+    rowptr = target_rowptr.detach().cpu().numpy() if torch.is_tensor(target_rowptr) \
+        else np.asarray(target_rowptr)
+    if rowptr.ndim != 1 or (rowptr.size and rowptr.dtype.kind not in "iu"):
+        raise engine.LgcnError("rank lists: target_rowptr must be 1-D integers")
+    rowptr = rowptr.astype(np.int64)
+    if rowptr.size != users.numel() + 1:
+        raise ValueError(f"rank lists: {users.numel()} users need {users.numel() + 1} offsets, "
+                         f"not {rowptr.size}")
+    lo, hi = int(rowptr[0]), int(rowptr[-1])
+    if (np.diff(rowptr) < 0).any() or lo < 0 or hi > items.numel():
+        raise ValueError("rank lists: target_rowptr must ascend inside target_items")
+    n_targets = int(items.numel())
+    rank = torch.full((n_targets,), -1, dtype=torch.int32, device=dev)
+    score = torch.full((n_targets,), float("nan"), dtype=torch.float32, device=dev)
+    lens = torch.from_numpy(np.diff(rowptr)).to(dev)
+    pair_users = torch.repeat_interleave(users, lens, output_size=hi - lo)
+    rank[lo:hi], score[lo:hi] = rank_torch(user_emb, item_emb, pair_users, items[lo:hi],
+                                           mask_rowptr, mask_items, batch_size)
+    return rank, score
+
+
+def metrics_from_rank_lists(ranks, rowptr, ks=(20,)):
+    """{'recall@k', 'precision@k', 'hit@k', 'ndcg@k' for k in ks, 'mrr'} from the 0-based ranks of
+    every held-out entry (a tensor or an array; -1 = no rank: a miss that still counts in its
+    user's list length) and the lists' offsets into them, each a mean over the users with a
+    non-empty list. With hits_k(u) the user's entries ranked below k and n_u its list length:
+    recall hits_k / n_u, precision hits_k / k, hit hits_k > 0, NDCG the DCG of the hits over the
+    DCG of min(k, n_u) hits at the first places, MRR 1 / (best rank + 1). With one entry per user
+    recall, NDCG and MRR are metrics_from_ranks' numbers to the bit. Empty input gives NaN."""
+    if torch.is_tensor(ranks):
+        ranks = ranks.detach().cpu().numpy()
+    if torch.is_tensor(rowptr):
+        rowptr = rowptr.detach().cpu().numpy()
+    rp = np.asarray(rowptr).astype(np.int64).reshape(-1)
+    r = np.asarray(ranks).astype(np.int64).reshape(-1)
+    lens = np.diff(rp) if rp.size else np.zeros(0, np.int64)
+    keep = lens > 0
+    n_u = lens[keep]
+    nu = int(n_u.size)
+    r = r[rp[0]:rp[-1]] if rp.size else r[:0]
+    seg = np.repeat(np.arange(nu), n_u)  # the entries' user among those with a list
+    nan = float("nan")
+    out = {}
+    for k in ks:
+        k = int(k)
+        found = (r >= 0) & (r < k)
+        pos = np.where(found, r, 0)
+        hits = np.bincount(seg, weights=found, minlength=nu)
+        dcg = np.bincount(seg, weights=np.where(found, 1.0 / np.log2(pos + 2), 0.0), minlength=nu)
+        top = int(min(k, n_u.max(initial=0)))
+        ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(top) + 2))])
+        out[f"recall@{k}"] = float((hits / n_u).mean()) if nu else nan
+        out[f"precision@{k}"] = float((hits / k).mean()) if nu else nan
+        out[f"hit@{k}"] = float((hits > 0).mean()) if nu else nan
+        out[f"ndcg@{k}"] = float((dcg / ideal[np.minimum(k, n_u)]).mean()) if nu else nan
+    if nu:
+        big = np.iinfo(np.int64).max
+        best = np.minimum.reduceat(np.where(r >= 0, r, big), (np.cumsum(n_u) - n_u))
+        ranked = best < big
+        rr = np.where(ranked, 1.0 / (np.where(ranked, best, 0) + 1), 0.0)
+    out["mrr"] = float(rr.mean()) if nu else nan
+    return out
+
+
 class Evaluator:
     """Evaluator(train_users, train_items, num_users, num_items, device)
 
@@ -335,9 +507,14 @@ class Evaluator:
 
         ev = Evaluator.from_sampler(sampler)          # or Evaluator(train_u, train_i, U, I, dev)
         metrics = ev.evaluate(model, adj, val_df, ks=(10, 20, 50))
+        metrics = ev.evaluate_lists(model, adj, test_df, ks=(10, 20, 50))  # every row of the frame
+
+    evaluate() keeps one held-out item per user (the last row of a user wins, as main.py's
+    dict(zip(...))); evaluate_lists() keeps them all and ranks a user's whole list from one pass.
 
     Device dispatch, as the sampler's: tables on a HIP device with a width in FUSED_DIMS run
-    lgcn_score_rank (no fallback for them), any other width and a CPU device run rank_torch."""
+    lgcn_score_rank / lgcn_score_rank_lists (no fallback for them), any other width and a CPU
+    device run rank_torch / rank_lists_torch."""
 
     def __init__(self, train_users, train_items, num_users, num_items, device):
         users = np.asarray(train_users, dtype=np.int64)
@@ -382,6 +559,20 @@ class Evaluator:
         self._init(rowptr, items, sampler.num_users, sampler.num_items, cls._device(sampler.device))
         return self
 
+    def _tables(self, model, adj):
+        """The model's propagated (user, item) tables in eval mode (call under no_grad), checked
+        against what this evaluator was built for."""
+        model.eval()
+        ue, ie = model(adj)[:2]
+        _check_tables(ue, ie)
+        if ie.device != self.device:
+            raise engine.LgcnError(f"Evaluator on {self.device}, the model's tables on "
+                                   f"{ie.device}")
+        if ue.shape[0] != self.num_users or ie.shape[0] != self.num_items:
+            raise engine.LgcnError(f"Evaluator for {self.num_users} x {self.num_items}, the "
+                                   f"model's tables are {ue.shape[0]} x {ie.shape[0]}")
+        return ue, ie
+
     def ranks(self, model, adj, eval_users, eval_items, batch_size=8192):
         """The rank of eval_items[j] for eval_users[j], as one int32 tensor on the device: one
         propagation under no_grad in model.eval() (left in eval mode, as main.py's evaluate leaves
@@ -390,16 +581,8 @@ class Evaluator:
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("Evaluator.ranks: batch_size must be positive")
-        model.eval()
         with torch.no_grad():
-            ue, ie = model(adj)[:2]
-            _check_tables(ue, ie)
-            if ie.device != self.device:
-                raise engine.LgcnError(f"Evaluator on {self.device}, the model's tables on "
-                                       f"{ie.device}")
-            if ue.shape[0] != self.num_users or ie.shape[0] != self.num_items:
-                raise engine.LgcnError(f"Evaluator for {self.num_users} x {self.num_items}, the "
-                                       f"model's tables are {ue.shape[0]} x {ie.shape[0]}")
+            ue, ie = self._tables(model, adj)
             if not (ie.is_cuda and ie.shape[1] in FUSED_DIMS):
                 return rank_torch(ue, ie, eval_users, eval_items, self._rowptr, self._items,
                                   min(batch_size, 1024))[0]
@@ -434,3 +617,53 @@ class Evaluator:
         else:
             users, items = eval_data
         return metrics_from_ranks(self.ranks(model, adj, users, items), ks)
+
+    def rank_lists(self, model, adj, eval_users, eval_items, batch_size=8192):
+        """Every held-out (user, item) pair ranked: (users int64, rowptr int32, ranks) with
+        target_csr's users and offsets as numpy and ranks an int32 tensor on the device, entry e
+        of user j at rowptr[j] <= e < rowptr[j+1] in item order. One propagation under no_grad in
+        model.eval(), the lists built once, then one lgcn_score_rank_lists per batch_size user
+        slots on pointer-offset views of the resident offsets (no per-batch copy, one scratch for
+        the largest batch). No read-back. A pair outside [0, num_users) x [0, num_items) ranks
+        -1."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("Evaluator.rank_lists: batch_size must be positive")
+        host = [a.detach().cpu().numpy() if torch.is_tensor(a) else a
+                for a in (eval_users, eval_items)]
+        eu, rowptr, items = target_csr(*host)
+        with torch.no_grad():
+            ue, ie = self._tables(model, adj)
+            if not (ie.is_cuda and ie.shape[1] in FUSED_DIMS):
+                return eu, rowptr, rank_lists_torch(ue, ie, eu, rowptr, items, self._rowptr,
+                                                    self._items, min(batch_size, 1024))[0]
+            users_t, rowptr_t, items_t = _list_slots(eu, rowptr, items, self.num_users,
+                                                     self.num_items, self.device)
+            n = len(eu)
+            rank = torch.full((len(items),), -1, dtype=torch.int32, device=self.device)
+            if n == 0:
+                return eu, rowptr, rank
+            lib = engine.load_library()
+            score = torch.empty(len(items), dtype=torch.float32, device=self.device)
+            cus = _device_cus(self.device)
+            batches = [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)]
+            splits = {e - s: lib.lgcn_eval_splits(e - s, self.num_items, cus) for s, e in batches}
+            scratch = torch.empty(max(lib.lgcn_score_rank_lists_scratch_bytes(
+                e - s, int(rowptr[e] - rowptr[s]), splits[e - s]) for s, e in batches),
+                dtype=torch.uint8, device=self.device)
+            ue, ie = _rows(ue), _rows(ie)
+            for s, e in batches:
+                _rank_lists_launch(ue, ie, users_t[s:e], rowptr_t[s:e + 1], items_t, self._rowptr,
+                                   self._items, rank, score, scratch, splits[e - s])
+        return eu, rowptr, rank
+
+    def evaluate_lists(self, model, adj, eval_data, ks=(20,)):
+        """metrics_from_rank_lists of rank_lists(): eval_data is a (users, items) pair, or a
+        DataFrame (any mapping) with 'user_idx' / 'item_idx'. Every row is kept: a user's list is
+        all its distinct held-out items. One read-back."""
+        if hasattr(eval_data, "keys") and "user_idx" in eval_data.keys():
+            users, items = np.asarray(eval_data["user_idx"]), np.asarray(eval_data["item_idx"])
+        else:
+            users, items = eval_data
+        _, rowptr, ranks = self.rank_lists(model, adj, users, items)
+        return metrics_from_rank_lists(ranks, rowptr, ks)

@@ -45,7 +45,8 @@ extern "C" {
 
 /* 14 since the sided propagation; the training-step entry points (lgcn_bpr_loss_indexed,
  * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) and the sampler (lgcn_bpr_sample,
- * LGCN_TUNE_SAMPLE_BLOCKS), the rank evaluation (lgcn_score_rank) and the brand-loss entry points
+ * LGCN_TUNE_SAMPLE_BLOCKS), the rank evaluation (lgcn_score_rank; lgcn_score_rank_lists and its
+ * scratch query for lists of held-out items) and the brand-loss entry points
  * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) were added without a bump:
  * purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
@@ -847,6 +848,35 @@ int lgcn_score_rank(const float* user_emb, int64_t ld_u, const int32_t* users, i
                     const int32_t* mask_rowptr, const int32_t* mask_items,
                     const int32_t* targets, int32_t n_splits, int32_t* part, float* target_score,
                     int32_t* rank, void* stream);
+
+/* Several held-out items per user, ranked from one pass over the user's score row. Slot b is user
+ * users[b]; its list is the entries e in [target_rowptr[b], target_rowptr[b+1]) of target_items.
+ * The offsets are absolute indices into target_items, target_score and rank, and target_rowptr[0]
+ * need not be 0: a batch of a larger set is target_rowptr + s with the same three base pointers.
+ * Entries outside [target_rowptr[0], target_rowptr[n_users]) are neither read nor written.
+ * For every entry e of slot b, rank[e] and target_score[e] equal, bit for bit, what lgcn_score_rank
+ * returns for the single slot (users[b], target_items[e]): -1e10 for a target that is a train
+ * item, rank -1 and a NaN score for a target outside [0, n_items); the other targets of the list
+ * count as ordinary items, a target listed twice gets its rank twice, a list may be in any order
+ * and may be empty (nothing is written), a user may appear in several slots. The result does not
+ * depend on n_splits, the slot, the order inside a list or the run.
+ * The item split is streamed once per 128 slots as long as no list of them has more than 32
+ * ranked entries, and once per 32 places of the longest list beyond that; any length works.
+ * scratch: lgcn_score_rank_lists_scratch_bytes(n_users, n_targets, n_splits) bytes, 4-B aligned,
+ * n_targets = target_rowptr[n_users] - target_rowptr[0] (0 bytes for arguments out of range). The
+ * call never reads target_rowptr on the host: a scratch below the size for n_targets = 0 is
+ * LGCN_EINVAL, and a slot whose entries lie past the entries the scratch holds is left unwritten.
+ * Widths, alignment, strides, n_splits and the order of the checks as lgcn_score_rank's;
+ * n_users == 0 returns 0 and touches no pointer. Allocates nothing, never synchronises, reads
+ * nothing back, everything on `stream` (capture-safe). */
+size_t lgcn_score_rank_lists_scratch_bytes(int32_t n_users, int64_t n_targets, int32_t n_splits);
+int lgcn_score_rank_lists(const float* user_emb, int64_t ld_u, const int32_t* users,
+                          int32_t n_users, const float* item_emb, int64_t ld_i,
+                          int32_t n_items, int32_t d,
+                          const int32_t* mask_rowptr, const int32_t* mask_items,
+                          const int32_t* target_rowptr, const int32_t* target_items,
+                          int32_t n_splits, void* scratch, size_t scratch_bytes,
+                          float* target_score, int32_t* rank, void* stream);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,11 @@ class LightGCN(nn.Module):
         (evaluate.Evaluator: the held-out item's exact rank per user, one read-back)."""
         return evaluator.evaluate(self, adj, (eval_users, eval_items), ks)
 
+    def evaluate_rank_lists(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
+        """Recall / precision / hit / NDCG @k and MRR over every held-out item of every user
+        (evaluate.Evaluator.evaluate_lists: all (user, item) rows are kept, one read-back)."""
+        return evaluator.evaluate_lists(self, adj, (eval_users, eval_items), ks)
+
     # -- LightGCN-style accessor (north_star "computer()") --------------------------------------
     def set_graph(self, adj_mat):
         self._graph_adj = adj_mat
