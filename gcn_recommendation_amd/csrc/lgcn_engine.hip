@@ -32,6 +32,7 @@ int g_mean_prefetch = 0;
 int g_min_groups = 0;
 int g_emu_margin = (128 << 4) | 4;  // LGCN_TUNE_EMU_MARGIN (the walk's prediction margin)
 int g_sample_blocks = 0;            // LGCN_TUNE_SAMPLE_BLOCKS (lgcn_sampler.hip's grid cap)
+int g_fusion_bwd_blocks = 0;        // LGCN_TUNE_FUSION_BWD_BLOCKS (lgcn_fusion_bwd.hip's grid cap)
 }  // namespace lgcn_detail
 
 namespace {
@@ -540,6 +541,11 @@ int lgcn_tune(int knob, int value) {
         case LGCN_TUNE_SAMPLE_BLOCKS: {
             const int old = lgcn_detail::g_sample_blocks;
             if (value >= 0) lgcn_detail::g_sample_blocks = value;
+            return old;
+        }
+        case LGCN_TUNE_FUSION_BWD_BLOCKS: {
+            const int old = lgcn_detail::g_fusion_bwd_blocks;
+            if (value >= 0) lgcn_detail::g_fusion_bwd_blocks = value;
             return old;
         }
         default:

@@ -27,6 +27,8 @@ INT32_MAX = 2 ** 31 - 1
 TUNE_ROWS_PER_GROUP, TUNE_UNROLL, TUNE_MEAN_PREFETCH, TUNE_MIN_GROUPS = 1, 2, 3, 4
 TUNE_EMU_MARGIN = 6
 TUNE_SAMPLE_BLOCKS = 7
+TUNE_FUSION_BWD_BLOCKS = 8
+FUSION_BWD_CHUNK = 2048  # LGCN_FUSION_BWD_CHUNK: rows per weight-gradient partial
 SCHED_SLOTS0, SCHED_SLOTS1, SCHED_CHAIN, SCHED_TIMING_START, SCHED_TIMING_END, SCHED_TRACE = \
     1, 2, 3, 4, 5, 6
 SCHED_TRACE_SIDES, SCHED_TIMING_SIDES = 7, 8
@@ -205,6 +207,10 @@ ABI = [
                                        ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P, _P, _P]),
     ("lgcn_fusion_prelayer", ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
+    ("lgcn_fusion_prelayer_backward_scratch_bytes", ctypes.c_size_t, [_I32, _I32, _I32]),
+    ("lgcn_fusion_prelayer_backward", ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32,
+                                                     _I32, _I32, _P, ctypes.c_float, _P, _I64, _P,
+                                                     _P, _P, ctypes.c_size_t, _P]),
     ("lgcn_chain_max_default", ctypes.c_int32, [_I64]),
     ("lgcn_chain_max_backward_default", ctypes.c_int32, [_I64]),
     ("lgcn_plan_exact", ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -4,9 +4,13 @@
 
 on a HIP device as one kernel (lgcn_fusion_prelayer: no concatenation, exact-f32 MFMA GEMM,
 bias + leaky_relu in its epilogue). The backward is the same arithmetic autograd would run for
-the reference expression, written out with torch ops (training only): g = dF where F > 0, else
-slope * dF; d_id = g · W[:, :d]; dW = gᵀ · [id | content]; db = Σ g. The content table is a
-buffer (no gradient), as in the reference.
+the reference expression: g = dF where F > 0, else slope * dF; d_id = g · W[:, :d];
+dW = gᵀ · [id | content]; db = Σ g. BACKWARD selects its route: "kernel" is
+lgcn_fusion_prelayer_backward (one pass, g masked in registers, both products on exact-f32 MFMA,
+dW and db summed in the fixed order include/lgcn.h documents: the same bits whatever the launch,
+the run or the device); "torch" is the expression written out with torch ops (two [I x d]
+temporaries and three library GEMMs, whose summation order the BLAS picks), kept for A/B timing
+and as the documented fallback. The content table is a buffer (no gradient), as in the reference.
 
 The backward reads the branch from the sign of the saved output, which equals the sign of z only
 for slope >= 0 (a negative z times a negative slope is positive). fused_item_embedding therefore
@@ -20,6 +24,9 @@ from . import engine
 
 SUPPORTED_D = (64, 128)
 SUPPORTED_C = (32, 64, 128)
+# The route of FusionPreLayer.backward: "kernel" | "torch". DESIGN.md section 8 has the measurement
+# the default rests on.
+BACKWARD = "kernel"
 
 
 def supported(d, c_dim):
@@ -62,6 +69,10 @@ class FusionPreLayer(torch.autograd.Function):
     def backward(ctx, g_out):
         idc, cc, wc, out = ctx.saved_tensors
         d = idc.shape[1]
+        if BACKWARD not in ("kernel", "torch"):
+            raise engine.LgcnError(f"fusion.BACKWARD = {BACKWARD!r}: expected 'kernel' or 'torch'")
+        if BACKWARD == "kernel" and out.is_cuda:
+            return _backward_kernel(ctx, idc, cc, wc, out, g_out)
         g = torch.where(out > 0, g_out, g_out * ctx.slope)
         d_id = g @ wc[:, :d] if ctx.needs_input_grad[0] else None
         d_w = None
@@ -69,6 +80,36 @@ class FusionPreLayer(torch.autograd.Function):
             d_w = torch.cat([g.t() @ idc, g.t() @ cc], 1)
         d_b = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[3] else None
         return d_id, None, d_w, d_b, None
+
+
+def _backward_kernel(ctx, idc, cc, wc, out, g_out):
+    """lgcn_fusion_prelayer_backward; each output is requested only when autograd needs it."""
+    lib = engine.load_library()
+    n, d = idc.shape
+    c_dim = cc.shape[1]
+    dev = out.device
+    want_id, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+    want_b = ctx.has_bias and ctx.needs_input_grad[3]
+    d_id = torch.empty((n, d), dtype=torch.float32, device=dev) if want_id else None
+    if n == 0:  # nothing to sum: the call would leave d_w and d_b unwritten
+        d_w = torch.zeros((d, d + c_dim), dtype=torch.float32, device=dev) if want_w else None
+        d_b = torch.zeros(d, dtype=torch.float32, device=dev) if want_b else None
+        return d_id, None, d_w, d_b, None
+    d_w = torch.empty((d, d + c_dim), dtype=torch.float32, device=dev) if want_w else None
+    d_b = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
+    gc = g_out.contiguous()
+    scratch, nbytes = None, 0
+    if want_w or want_b:
+        nbytes = lib.lgcn_fusion_prelayer_backward_scratch_bytes(n, d, c_dim)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        engine._check(lib.lgcn_fusion_prelayer_backward(
+            engine._ptr(out), d, engine._ptr(gc), d, engine._ptr(idc), d, engine._ptr(cc), c_dim,
+            n, d, c_dim, engine._ptr(wc),
+            float(ctx.slope), engine._ptr(d_id), d, engine._ptr(d_w), engine._ptr(d_b),
+            engine._ptr(scratch), nbytes, engine._stream(dev)),
+            "lgcn_fusion_prelayer_backward")
+    return d_id, None, d_w, d_b, None
 
 
 def fused_item_embedding(id_w, content, linear, slope=0.01):

@@ -47,7 +47,9 @@ extern "C" {
  * lgcn_bpr_keys, lgcn_rows_scatter, lgcn_rows_clear) and the sampler (lgcn_bpr_sample,
  * LGCN_TUNE_SAMPLE_BLOCKS), the rank evaluation (lgcn_score_rank; lgcn_score_rank_lists and its
  * scratch query for lists of held-out items) and the brand-loss entry points
- * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) were added without a bump:
+ * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) and the fusion pre-layer's
+ * backward (lgcn_fusion_prelayer_backward, its scratch query, LGCN_FUSION_BWD_CHUNK,
+ * LGCN_TUNE_FUSION_BWD_BLOCKS) were added without a bump:
  * purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
@@ -261,6 +263,9 @@ const char* lgcn_error_string(int code);
 #define LGCN_TUNE_SAMPLE_BLOCKS  7  /* lgcn_bpr_sample: the most blocks (of 256 slots per pass) its
                                        grid-stride launch uses (0 = auto = 8 per CU); a draw never
                                        depends on the launch geometry */
+#define LGCN_TUNE_FUSION_BWD_BLOCKS 8 /* lgcn_fusion_prelayer_backward: the most blocks its main
+                                       kernel's grid uses (0 = auto = one per CU); block b walks
+                                       the row chunks b, b + grid, ...: no bit depends on it */
 int lgcn_tune(int knob, int value);
 
 /* device properties the host side needs (CU count); returns 0/hipError */
@@ -803,6 +808,59 @@ int lgcn_fusion_prelayer(const float* id_emb, int64_t ld_id, const float* conten
                          int32_t n_items, int32_t d, int32_t c_dim, const float* weight,
                          const float* bias, float slope, float* out, int64_t ld_out,
                          void* stream);
+
+/* The pre-layer's backward: from the forward's saved output `out` and g_out = dL/d out
+ * ([n_items x d] each), with x = [id_emb | content] and weight W [d x (d + c_dim)] dense:
+ *   g[i,o]    = out[i,o] > 0 ? g_out[i,o] : fp32(g_out[i,o] * slope)
+ *   d_id[i,k] = sum_o g[i,o] * W[o,k], k < d      d_w[o,k] = sum_i g[i,o] * x[i,k]
+ *   d_b[o]    = sum_i g[i,o]
+ * Each of d_id / d_w / d_b may be NULL (= not wanted). g is formed in registers and never stored.
+ * A zero of either sign or a NaN in `out` takes the slope branch (torch.where(out > 0, ...)). The
+ * branch is read from `out`, which has the sign of the pre-activation only for slope >= 0: a
+ * caller with slope < 0 must not use this entry (fusion.py refuses it).
+ * Both products run on exact-f32 MFMA: every sum below is an fp32 fmaf chain (one rounding per
+ * term). No float atomics.
+ *  - d_id[i,k]: one chain from +0 over o = 0, 1, ..., d-1. It does not depend on where row i
+ *    sits, on n_items or on the launch; a NaN or an infinity stays inside its row.
+ *  - d_w / d_b: the rows are cut into chunks of LGCN_FUSION_BWD_CHUNK consecutive rows, chunk c =
+ *    rows [c*CHUNK, min((c+1)*CHUNK, n_items)), a chunk into tiles of 32 consecutive rows (the
+ *    last one of the last chunk padded with +0 terms, which change no bit).
+ *      d_w partial of a chunk: ONE chain from +0 over its tiles in ascending order, the rows of a
+ *        tile in the order 0, 16, 1, 17, ..., 15, 31 (at most CHUNK roundings).
+ *      d_b partial of a chunk: two plain fp32 sums from +0, `lo` over the rows 0..15 of every
+ *        tile and `hi` over the rows 16..31 of every tile, each in ascending row order; the
+ *        partial is lo + hi (at most CHUNK/2 + 1 roundings).
+ *      Combine, a fixed two-level tree: the partials of every 32 consecutive chunks (chunks
+ *        [32j, 32j+32)) are added in ascending order from +0; then the group sums in ascending j
+ *        from +0 (at most min(32, n_chunks) + ceil(n_chunks/32) roundings, no more than
+ *        n_chunks + 1).
+ *    The longest path of a d_w element, the rounding of g_out * slope included, is therefore
+ *    R <= CHUNK + n_chunks + 2 roundings, n_chunks = ceil(n_items / CHUNK). The bits depend on
+ *    the inputs and n_items only: not on the grid (LGCN_TUNE_FUSION_BWD_BLOCKS), the CU count,
+ *    the stream, the run, or which of d_id / d_w / d_b were requested.
+ * Shapes as the forward's: d in {64, 128}, c_dim in {32, 64, 128}. out, g_out, id_emb, content
+ * and d_id: 16-B aligned rows (pointer and leading dim); weight, d_w [d x (d + c_dim)] dense and
+ * d_b [d] are accessed by element. Reads only rows < n_items; writes exactly d_id[i, 0..d) for
+ * i < n_items, d_w[0 .. d*(d+c_dim)) and d_b[0..d). ld_did is looked at only when d_id is wanted.
+ * scratch (needed only when d_w or d_b is wanted; 4-B aligned, contents opaque):
+ * lgcn_fusion_prelayer_backward_scratch_bytes(n_items, d, c_dim) bytes — one slot per chunk, so
+ * constant inside a chunk and non-decreasing in n_items; 0 for arguments out of range.
+ * Checks, in this order, all on the host before any launch: n_items < 0, d or c_dim unsupported,
+ * a leading dim below its width or above 2^24 floats (the kernel addresses the 32 rows of a tile
+ * with 32-bit byte offsets) (LGCN_EINVAL); then n_items == 0 returns 0, launches nothing and
+ * looks at no pointer (the caller owns zeroing d_w and d_b); then all three outputs NULL returns
+ * 0 and launches nothing; then out, g_out, id_emb, content or weight NULL, or, while d_w or d_b
+ * is wanted, scratch NULL or scratch_bytes too small (LGCN_EINVAL); then out, g_out, id_emb,
+ * content or d_id not 16-B aligned, or a leading dim not a multiple of 4 (LGCN_EALIGN).
+ * Allocates nothing, never synchronises, everything on `stream` (capture-safe). */
+#define LGCN_FUSION_BWD_CHUNK 2048   /* fixed at build time; a power of two, <= 8192 */
+size_t lgcn_fusion_prelayer_backward_scratch_bytes(int32_t n_items, int32_t d, int32_t c_dim);
+int lgcn_fusion_prelayer_backward(const float* out, int64_t ld_out, const float* g_out,
+                                  int64_t ld_g, const float* id_emb, int64_t ld_id,
+                                  const float* content, int64_t ld_c, int32_t n_items, int32_t d,
+                                  int32_t c_dim, const float* weight, float slope, float* d_id,
+                                  int64_t ld_did, float* d_w, float* d_b, void* scratch,
+                                  size_t scratch_bytes, void* stream);
 
 /* ---- evaluation (main.py:404-439) ----------------------------------------------------------- */
 /* Item splits for lgcn_score_topk and lgcn_score_rank: ~2 blocks per CU, >= 2048 items per split,
