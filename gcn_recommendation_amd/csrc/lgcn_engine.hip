@@ -364,9 +364,10 @@ struct CombineF {
 };
 
 struct ScaleF {
-    const lgcn_rows_t* x; int32_t n; int32_t dW; float div; float* y; int64_t ldy; hipStream_t s;
+    const lgcn_rows_t* x; int32_t n; int32_t dW; float div; float* y; int64_t ldy; bool sum;
+    hipStream_t s;
     template <typename V, int G, int NV> int operator()() const {
-        return launch_scale_t<V, G, NV>(*x, n, dW, div, y, ldy, s);
+        return launch_scale_t<V, G, NV>(*x, n, dW, div, y, ldy, sum, s);
     }
 };
 
@@ -438,11 +439,12 @@ int hub_combine(const lgcn_hub_row_t* rows, int32_t n, int32_t n_pre, float* par
     return dispatch_geo(g, f);
 }
 
+// sum: y = (+0 + x) / div, the mean of one stacked layer (k_scale_rows)
 int scale_rows(const lgcn_rows_t& x, int32_t n_rows, int32_t d, float div, float* y, int64_t ldy,
-               hipStream_t s) {
+               hipStream_t s, bool sum = false) {
     const bool vec_ok = rows_aligned(x) && al16(y) && (ldy % 4 == 0);
     const Geo g = pick_geo(d, vec_ok);
-    ScaleF f{&x, n_rows, g.dW, div, y, ldy, s};
+    ScaleF f{&x, n_rows, g.dW, div, y, ldy, sum, s};
     return dispatch_geo(g, f);
 }
 
@@ -1825,10 +1827,11 @@ int lgcn_propagate_forward(const int32_t* rowptr, const lgcn_edge_t* edges,
                            int32_t K, float* const* layer_bufs_host, float* out,
                            void* const* ev_host, const lgcn_sched_t* sched, void* stream) {
     if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || K - 1 > LGCN_MAX_LAYERS || !out) return K < 0 || !out ? LGCN_EINVAL : LGCN_ETOOMANY;
+    if (K < 0 || !out) return LGCN_EINVAL;
+    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
     if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
     hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s);
+    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
     if (int e = check_plan(plan)) return e;
     if (sched) sched->pool->next = 0;
     for (int k = 1; k <= K; ++k) {
@@ -1878,10 +1881,11 @@ int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* 
                                       const lgcn_sched_t* sched, void* stream) {
     const int32_t n = sides ? sides->n : -1;
     if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || K - 1 > LGCN_MAX_LAYERS || !out) return K < 0 || !out ? LGCN_EINVAL : LGCN_ETOOMANY;
+    if (K < 0 || !out) return LGCN_EINVAL;
+    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
     if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
     hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s);
+    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
     if (int e = check_sides(rowptr, row_ids, n, sides, plans)) return e;
     auto layer = [&](int k) {
         LayerIO io;
@@ -1920,6 +1924,7 @@ int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edge
     const int32_t n = sides ? sides->n : -1;
     if (int e = valid_geom(n, d)) return e;
     if (K < 0 || !grad_out.p0 || !grad_e0) return LGCN_EINVAL;
+    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // the backward of a forward that is refused
     hipStream_t s = S(stream);
     if (K == 0) return scale_rows(grad_out, n, d, 1.0f, grad_e0, d, s);
     if (K > 1 && !work_h) return LGCN_EINVAL;
@@ -1951,6 +1956,7 @@ int lgcn_propagate_backward(const int32_t* rowptr, const lgcn_edge_t* edges,
                             float* grad_e0, const lgcn_sched_t* sched, void* stream) {
     if (int e = valid_geom(n, d)) return e;
     if (K < 0 || !grad_out.p0 || !grad_e0) return LGCN_EINVAL;
+    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // the backward of a forward that is refused
     hipStream_t s = S(stream);
     if (K == 0) return scale_rows(grad_out, n, d, 1.0f, grad_e0, d, s);
     if (K > 1 && !work_h) return LGCN_EINVAL;

@@ -949,7 +949,7 @@ __global__ __launch_bounds__(64) void k_emu_walk(const lgcn_edge_t* __restrict__
     }
     if constexpr (MODE == LGCN_EPI_MEAN) {
         // ((E0 + E1) + ... + E_{K-1}) + E_K, then / (K+1)  (lightgcn.py:54)
-        float s = seg_row_x(ep.prev0, row)[c];
+        float s = 0.f + seg_row_x(ep.prev0, row)[c];  // ATen's sum starts from +0
         for (int i = 0; i + 1 < ep.n_prev; ++i) s = s + ep.prev_dense[i][(int64_t)row * ep.ld_prev + c];
         s = s + out;
         out = ep.pad ? s * __int_as_float(ep.pad) : s / ep.div;
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(64) void k_chain_rows(const lgcn_edge_t* __restrict
         return;
     }
     if constexpr (MODE == LGCN_EPI_MEAN) {
-        float s = seg_row_x(ep.prev0, row)[c];
+        float s = 0.f + seg_row_x(ep.prev0, row)[c];  // ATen's sum starts from +0
         for (int i = 0; i + 1 < ep.n_prev; ++i) s = s + ep.prev_dense[i][(int64_t)row * ep.ld_prev + c];
         s = s + out;
         out = ep.pad ? s * __int_as_float(ep.pad) : s / ep.div;
@@ -1269,7 +1269,7 @@ __global__ __launch_bounds__(256) void k_emu_epilogue(const lgcn_emu_row_t* __re
     for (int c = threadIdx.x; c < d; c += blockDim.x) {
         float out = tmp[(int64_t)blockIdx.x * ldt + c];
         if constexpr (MODE == LGCN_EPI_MEAN) {
-            float s = seg_row_x(ep.prev0, row)[c];
+            float s = 0.f + seg_row_x(ep.prev0, row)[c];  // ATen's sum starts from +0
             for (int i = 0; i + 1 < ep.n_prev; ++i)
                 s = s + ep.prev_dense[i][(int64_t)row * ep.ld_prev + c];
             s = s + out;

@@ -267,8 +267,10 @@ __device__ __forceinline__ void epilogue_store(const lgcn_epilogue_t& ep, int32_
         if (c >= dW) continue;
         V out = acc[q];
         if constexpr (MODE == LGCN_EPI_MEAN) {
-            // ((E0 + E1) + ... + E_{K-1}) + E_K, then / (K+1): torch.mean(torch.stack(.), 0)
-            V s = load_stream<V>(seg_row(ep.prev0, row) + c * T::W);
+            // (((+0 + E0) + E1) + ... + E_{K-1}) + E_K, then / (K+1): torch.mean(torch.stack(.), 0).
+            // ATen's sum starts from +0: an element that is -0 in every layer (E0 and chains
+            // that underflowed to -0) comes out +0
+            V s = T::add(T::zero(), load_stream<V>(seg_row(ep.prev0, row) + c * T::W));
             for (int i = 0; i + 1 < ep.n_prev; ++i)
                 s = T::add(s, load_stream<V>(ep.prev_dense[i] + (int64_t)row * ep.ld_prev + c * T::W));
             s = T::add(s, out);
@@ -372,7 +374,7 @@ __device__ __forceinline__ void rows_bundle(const int32_t* __restrict__ rowptr,
         const int32_t deg = bnd(i + 1) - bnd(i);
         const int32_t orow = __shfl(orl, i, G);
         if constexpr (PRE) {
-            // ((E0 + E1) + ... + E_{K-1}) + E_K, then / (K+1) — epilogue_store's order
+            // (((+0 + E0) + E1) + ... + E_{K-1}) + E_K, then / (K+1) — epilogue_store's order
             const int s = (i * dW) / G;                 // the row's slot, uniform in the group
             const int src = (i * dW + lane) & (G - 1);  // lane holding column `lane` of row i
             V sum = T::zero();
@@ -383,7 +385,7 @@ __device__ __forceinline__ void rows_bundle(const int32_t* __restrict__ rowptr,
                 for (int q = 1; q < RPG; ++q)
                     if (q == s) v = pre[p][q];
                 v = shfl_v<V>(v, src, G);
-                sum = p == 0 ? v : T::add(sum, v);
+                sum = T::add(sum, v);
             }
             if (deg <= hub_thr && lane < dW)
                 store_out<V>(y + (int64_t)orow * ldy + lane * T::W,
@@ -539,7 +541,7 @@ __global__ __launch_bounds__(kBlock) void k_layer(
             for (int q = 0; q < NV; ++q) {
                 const int c = lane + q * G;
                 if (c >= dW) continue;
-                V s = pre[0][q];
+                V s = T::add(T::zero(), pre[0][q]);  // from +0, as epilogue_store
 #pragma unroll
                 for (int p = 1; p < NP; ++p) s = T::add(s, pre[p][q]);
                 store_out<V>(yr + c * T::W, div_exact<V>(T::add(s, acc[q]), ep.div, ep.pad));
@@ -605,7 +607,9 @@ __global__ __launch_bounds__(kBlock) void k_hub_combine(const lgcn_hub_row_t* __
     epilogue_store<V, G, NV, MODE>(ep, hr.row, lane, dW, acc, y, ldy);
 }
 
-template <typename V, int G, int NV>
+// SUM: the mean of ONE stacked layer (the forward at K = 0), (+0 + x) / div — ATen's sum starts
+// from +0, so a -0 of E0 comes out as +0. Without it x / div keeps the sign (MeanBackward).
+template <typename V, int G, int NV, bool SUM = false>
 __global__ __launch_bounds__(kBlock) void k_scale_rows(lgcn_rows_t x, int32_t n_rows, int32_t dW,
                                                        float div, float* __restrict__ y,
                                                        int64_t ldy) {
@@ -618,7 +622,10 @@ __global__ __launch_bounds__(kBlock) void k_scale_rows(lgcn_rows_t x, int32_t n_
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
         const int c = lane + q * G;
-        if (c < dW) T::store(y + (int64_t)row * ldy + c * T::W, T::div(T::load(xr + c * T::W), div));
+        if (c >= dW) continue;
+        V v = T::load(xr + c * T::W);
+        if constexpr (SUM) v = T::add(T::zero(), v);
+        T::store(y + (int64_t)row * ldy + c * T::W, T::div(v, div));
     }
 }
 
@@ -854,12 +861,16 @@ int launch_combine_t(const lgcn_hub_row_t* rows, int32_t n, const float* partial
 
 template <typename V, int G, int NV>
 int launch_scale_t(const lgcn_rows_t& x, int32_t n_rows, int32_t dW, float div, float* y,
-                   int64_t ldy, hipStream_t s) {
+                   int64_t ldy, bool sum, hipStream_t s) {
     constexpr int RPB = kBlock / G;
     const int64_t grid = ((int64_t)n_rows + RPB - 1) / RPB;
     if (grid == 0) return 0;
-    hipLaunchKernelGGL((k_scale_rows<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, x, n_rows,
-                       dW, div, y, ldy);
+    if (sum)
+        hipLaunchKernelGGL((k_scale_rows<V, G, NV, true>), dim3((uint32_t)grid), dim3(kBlock), 0,
+                           s, x, n_rows, dW, div, y, ldy);
+    else
+        hipLaunchKernelGGL((k_scale_rows<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, x,
+                           n_rows, dW, div, y, ldy);
     return last_err();
 }
 

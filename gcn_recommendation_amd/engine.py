@@ -1413,6 +1413,13 @@ def _collect_sides(ev, K, graph):
                            for k in range(1, K + 1) for g in segs})
 
 
+def _check_depth(K):
+    """K = 0..LGCN_MAX_LAYERS: torch.mean over 18 stacked layers (K = 17) no longer sums them
+    one after the other, so the forward and its backward stop at 16."""
+    if K > LGCN_MAX_LAYERS or K < 0:
+        raise LgcnError(f"n_layers={K} unsupported (0..{LGCN_MAX_LAYERS})")
+
+
 def alloc_layers(n, d, count, device):
     """The forward's intermediate layer buffers (a test replaces this to see which rows a lean
     forward leaves unwritten)."""
@@ -1442,16 +1449,17 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
     if n != graph.n_rows:
         raise LgcnError(f"embedding rows {n} != adjacency size {graph.n_rows}")
     _check_emb(segments, d, graph.device)
-    if K > LGCN_MAX_LAYERS + 1 or K < 0:
-        raise LgcnError(f"n_layers={K} unsupported (0..{LGCN_MAX_LAYERS + 1})")
+    _check_depth(K)
     lib = load_library()
     dev = graph.device
     with torch.cuda.device(dev):
         stream = _stream(dev)
         e0 = rows_desc(segments, d)
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
-        if K == 0:
-            _check(lib.lgcn_scale_rows(e0, n, d, 1.0, _ptr(out), d, stream), "lgcn_scale_rows")
+        if K == 0:  # mean(stack([E0])) = (+0 + E0) / 1: no graph, plan or layer buffer is read
+            _check(lib.lgcn_propagate_forward(None, None, None, n, None, e0, d, 0, None,
+                                              _ptr(out), None, None, stream),
+                   "lgcn_propagate_forward")
             return (out, []) if return_layers else out
         layers = alloc_layers(n, d, K - 1, dev)
         if use_sides(graph, layer_events, kernel_events):
@@ -1633,6 +1641,7 @@ def propagate_backward(graph, grad_out, K, hub_threshold=None, sparse=None, hub_
     d = segs[0].shape[1]
     n = sum(int(t.shape[0]) for t in segs)
     _check_emb(segs, d, graph.device)
+    _check_depth(K)
     lib = load_library()
     dev = graph.device
     with torch.cuda.device(dev):

@@ -32,6 +32,16 @@
  *    items): short rows run that chain directly, rows of any length up to millions of edges are
  *    reproduced by block emulation (lgcn_emu_*). Hub CHUNK items are the optional fast mode: a
  *    long row cut into fixed chunks summed in a fixed order (deterministic, not bitwise).
+ *  - Range of that guarantee: K = 0..16 (LGCN_MAX_LAYERS; K = 17 is refused with LGCN_ETOOMANY:
+ *    over 18 stacked layers torch.mean no longer sums them one after the other), d = 1..2048.
+ *    Every layer E1..EK and every gradient is bitwise for every K of the range. The final
+ *    mean is bitwise the reference's everywhere for K <= 3; for K = 4..16 everywhere except the
+ *    last n*d mod 32 elements of the flattened [n x d] table (32 measured with torch
+ *    2.10.0+rocm7.0, AVX512; the width belongs to the ATen build). On that tail ATen itself
+ *    leaves the sequential order (four interleaved partial sums); the engine keeps
+ *    (((+0 + E0) + E1) + ... + EK) / (K+1) there too (DESIGN.md §3,
+ *    tests/test_reference_mean.py). The sum starts from +0 as ATen's does, K = 0 included: an
+ *    element that is -0 in every layer has the mean +0.
  */
 #ifndef LGCN_H_
 #define LGCN_H_
@@ -56,10 +66,13 @@ extern "C" {
 /* engine error codes (negative; positive values are hipError_t) */
 #define LGCN_EINVAL      (-1)   /* bad size / null pointer / unsupported dimension */
 #define LGCN_EALIGN      (-2)   /* a vectorised path needs 16-B aligned rows; see engine.py */
-#define LGCN_ETOOMANY    (-3)   /* more than LGCN_MAX_LAYERS previous layers in a mean epilogue,
-                                   or a schedule's event pool exhausted by one call */
+#define LGCN_ETOOMANY    (-3)   /* K > LGCN_MAX_LAYERS in a propagation entry point, more than
+                                   LGCN_MAX_LAYERS prev_dense rows in a mean epilogue, or a
+                                   schedule's event pool exhausted by one call */
 
-#define LGCN_MAX_LAYERS 16      /* torch.mean over <= 17 stacked layers sums them sequentially */
+#define LGCN_MAX_LAYERS 16      /* the deepest K: torch.mean over K+1 <= 17 stacked layers sums
+                                   them sequentially (but for a short tail, see Numerics), over 18
+                                   it does not; also the size of lgcn_epilogue_t.prev_dense */
 
 /* status flags written by lgcn_coo_inspect */
 #define LGCN_COO_ROWS_UNSORTED   1  /* some row index decreases in stored order */
@@ -414,7 +427,8 @@ int lgcn_hub_combine(const lgcn_hub_row_t* hub_rows, int32_t n_hub_rows, int32_t
 int lgcn_rows_nonzero(lgcn_rows_t x, int32_t n_rows, int32_t d, uint32_t* mask, int32_t* count,
                       void* stream);
 
-/* Y[r,:] = X[r,:] / div for r < n_rows (mean of one layer; backward seed G/(K+1)). */
+/* Y[r,:] = X[r,:] / div for r < n_rows (the backward seed G/(K+1); a -0 keeps its sign. The
+ * forward at K = 0 is lgcn_propagate_forward's (+0 + X) / 1, the mean of one stacked layer). */
 /* dst[i] = dst[i] + src[i] wherever src[i] != 0 (n floats each): the gradient of layer-0 rows a
  * training step gathers (main.py:497, a row-sparse [rows x d] block) accumulated into the
  * propagation's dense gradient — the autograd accumulation of the two, reading dst only where src
@@ -563,7 +577,8 @@ int lgcn_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
 /* Whole forward in one call: E1..E_{K-1} into layer_bufs_host[0..K-2] (each [n x d], ld = d),
  * final = mean(E0..EK) into out [n x d]. emb = E0 segments. plan: as in lgcn_layer (its
  * scratch sized for d). ev_host: NULL or 2*K hipEvent_t recorded around each layer (timing
- * only). sched: as in lgcn_layer. */
+ * only). sched: as in lgcn_layer. K = 0..LGCN_MAX_LAYERS: a larger K returns LGCN_ETOOMANY, here
+ * and in every lgcn_propagate_* entry point below, before anything is looked at or launched. */
 int lgcn_propagate_forward(const int32_t* rowptr, const lgcn_edge_t* edges,
                            const int32_t* row_ids, int32_t n, const lgcn_hub_plan_t* plan,
                            lgcn_rows_t emb, int32_t d,

@@ -65,7 +65,9 @@ void oracle_forward(int64_t nnz, const int64_t* rows, const int64_t* cols, const
     const size_t sz = (size_t)(n * d);
     float* prev = (float*)malloc(sizeof(float) * (sz ? sz : 1));
     float* cur = (float*)malloc(sizeof(float) * (sz ? sz : 1));
-    memcpy(final_out, e0, sizeof(float) * sz);  /* running sum starts at E0 */
+    /* ATen's sum starts from +0: +0 + E0 is E0 but for a -0, which becomes +0. It shows at K = 0
+     * only (for K >= 1, E1 is never -0 and the first add does the same). */
+    for (size_t i = 0; i < sz; ++i) final_out[i] = 0.0f + e0[i];
     memcpy(prev, e0, sizeof(float) * sz);
     for (int64_t k = 0; k < K; ++k) {
         oracle_spmm_coo(nnz, rows, cols, vals, n, d, prev, cur);

@@ -72,6 +72,25 @@ def test_argument_validation_without_gpu(lib):
     assert lib.lgcn_rows_nonzero(engine.RowsT(), 10, 0, None, None, None) == -1
     assert lib.lgcn_propagate_forward(None, None, None, 5, None, rows, 64, -1,
                                       None, None, None, None, None) == -1
+    # K = 17 (18 stacked layers: torch.mean leaves the sequential sum) is refused by every
+    # propagation entry point before it looks at a plan or a device; K = 16 gets past that check
+    sd17 = engine.SidesT()
+    sd17.n = 5
+    some = ctypes.c_void_p(8)
+    g17 = engine.RowsT()
+    g17.p0 = 8
+    for K, rc in ((17, -3), (18, -3), (16, -1)):
+        assert lib.lgcn_propagate_forward(None, None, None, 5, None, rows, 64, K,
+                                          some, some, None, None, None) == rc, K
+        assert lib.lgcn_propagate_forward_sides(None, None, None, ctypes.byref(sd17), None, rows,
+                                                64, K, some, some, None, None) == rc, K
+        assert lib.lgcn_propagate_forward_sides_lean(None, None, None, ctypes.byref(sd17), None,
+                                                     None, rows, 64, K, some, some, None,
+                                                     None) == rc, K
+        assert lib.lgcn_propagate_backward(None, None, None, 5, None, g17, None, 64, K, some,
+                                           some, None, None) == rc, K
+        assert lib.lgcn_propagate_backward_sides(None, None, None, ctypes.byref(sd17), None, g17,
+                                                 None, 64, K, some, some, None, None) == rc, K
     plan = engine.PlanT()
     plan.n_emu_rows = 3  # emulated rows without their buffers
     ep.mode = engine.LGCN_EPI_STORE

@@ -51,6 +51,31 @@ def assert_close_normwise(got, ref, tol=1e-5, what=""):
     assert err <= tol * max(scale, 1e-30), f"{what}: max|d|={err:.3e} > {tol}*{scale:.3e}"
 
 
+def stacked_mean_torch_order(layers, tail_width):
+    """torch.mean(torch.stack(layers, 0), 0) on the CPU for 2..17 float32 layers of one shape,
+    restated in numpy float32 (measured: tests/test_reference_mean.py). Over the flattened
+    [n*d] result ATen sums the layers one after the other from +0 below
+    cut = (n*d // tail_width) * tail_width. From cut on its row_sum keeps four partial sums from
+    +0, p[k] += layer[4*j + k] over the complete groups of four layers, adds the leftover layers
+    into p[0] in order and returns ((p0 + p1) + p2) + p3. Then the divide by the layer count.
+    tail_width belongs to the ATen build (its vector width times its unroll)."""
+    x = np.stack([np.asarray(a, dtype=np.float32) for a in layers])
+    shape = x.shape[1:]
+    x = x.reshape(x.shape[0], -1)
+    L, m = x.shape
+    cut = (m // tail_width) * tail_width
+    s = np.zeros(m, np.float32)
+    for i in range(L):
+        s[:cut] = s[:cut] + x[i, :cut]
+    p = np.zeros((4, m - cut), np.float32)
+    for i in range(L - L % 4):
+        p[i % 4] = p[i % 4] + x[i, cut:]
+    for i in range(L - L % 4, L):
+        p[0] = p[0] + x[i, cut:]
+    s[cut:] = ((p[0] + p[1]) + p[2]) + p[3]
+    return (s / np.float32(L)).reshape(shape)
+
+
 # ---- fusion pre-layer and BPR loss references (float64, plain numpy) ----------------------------
 U32 = 2.0 ** -24  # unit roundoff of fp32
 
