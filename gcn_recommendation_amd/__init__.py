@@ -6,6 +6,7 @@
     train    bpr_step: one fused BPR training step that keeps the batch indices (main.py:495-525);
              bpr_epoch: a whole epoch of them fed by the sampler
     sampler  BprSampler: the negatives of a whole epoch in one launch (main.py:349-363)
+    optim    Adam: torch.optim.Adam's default step, bit for bit, as one launch (main.py's optimizer)
     dist     multi-GPU propagation (row partition + per-layer RCCL all-gather; feature split)
 """
 __version__ = "0.1.0"
@@ -17,10 +18,10 @@ import sys as _sys
 
 
 def __getattr__(name):
-    # `gcn_recommendation_amd.sampler` on first use: importing the package itself still imports
-    # neither torch nor the engine
-    if name == "sampler":
-        return _importlib.import_module(f"{__name__}.sampler")
+    # `gcn_recommendation_amd.sampler` / `.optim` on first use: importing the package itself still
+    # imports neither torch nor the engine
+    if name in ("sampler", "optim"):
+        return _importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

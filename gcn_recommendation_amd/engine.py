@@ -44,6 +44,7 @@ TRACE_PHASES = ("start", "part0_blocks", "part1_blocks", "layer_kernel", "chain_
                 "part0_walk", "part1_walk", "joined")
 ABI_VERSION = 14
 LGCN_EMU_CANDS, LGCN_EMU_META_BYTES, LGCN_EMU_BLOCK = 16, 16, 256
+ADAM_MAX_TENSORS, ADAM_CHUNK = 16, 4096  # LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK
 
 # Rows up to this degree run as row bundles in the layer kernel (one sequential fmaf chain each,
 # bitwise = reference CPU path). Longer rows ("hubs") follow the hub mode:
@@ -152,6 +153,20 @@ class SidesT(ctypes.Structure):
 class LeanT(ctypes.Structure):
     """lgcn_lean_t"""
     _fields_ = [("empty_tail", ctypes.c_int32 * 4)]
+
+
+class AdamTensorT(ctypes.Structure):
+    """lgcn_adam_tensor_t"""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p),
+                ("v", ctypes.c_void_p), ("n", ctypes.c_int64), ("step_size", ctypes.c_double),
+                ("bc2_sqrt", ctypes.c_double)]
+
+
+class AdamHyperT(ctypes.Structure):
+    """lgcn_adam_hyper_t"""
+    _fields_ = [("lerp_w", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("one_minus_beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
 
 
 class LgcnError(RuntimeError):
@@ -265,6 +280,9 @@ ABI = [
     ("lgcn_propagate_backward_sides", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(SidesT),
                                                      ctypes.POINTER(PlanT), RowsT, _P, _I32, _I32,
                                                      _P, _P, _P, _P]),
+    ("lgcn_adam_step", ctypes.c_int, [ctypes.POINTER(AdamTensorT), _I32,
+                                      ctypes.POINTER(AdamHyperT), _P]),
+    ("lgcn_adam_chunks", ctypes.c_int64, [_I64]),
 ]
 
 

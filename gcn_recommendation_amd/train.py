@@ -400,7 +400,9 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     whose user has no free item carries neg = -1: on a HIP device bpr_step skips it
     (sampler.unsampled counts them); on a CPU adjacency, where the reference's own indexing would
     take -1 for the last item, it raises before the first optimizer step. item_brand and
-    brand_loss_weight are bpr_step's: the brand loss of every batch, looked up on the device."""
+    brand_loss_weight are bpr_step's: the brand loss of every batch, looked up on the device.
+    Any optimizer works; `optim.Adam(model.parameters(), lr)` keeps the whole step inside the
+    engine (one launch, lgcn_adam_step) and leaves torch.optim.Adam's bits."""
     if sampler.device != adj.device:
         raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
     batches = sampler.epoch(epoch, batch_size, shuffle=shuffle)  # the draw is made here

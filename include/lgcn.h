@@ -59,7 +59,8 @@ extern "C" {
  * scratch query for lists of held-out items) and the brand-loss entry points
  * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) and the fusion pre-layer's
  * backward (lgcn_fusion_prelayer_backward, its scratch query, LGCN_FUSION_BWD_CHUNK,
- * LGCN_TUNE_FUSION_BWD_BLOCKS) were added without a bump:
+ * LGCN_TUNE_FUSION_BWD_BLOCKS) and the Adam step (lgcn_adam_step, lgcn_adam_chunks, their two
+ * structs, LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK) were added without a bump:
  * purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
@@ -950,6 +951,51 @@ int lgcn_score_rank_lists(const float* user_emb, int64_t ld_u, const int32_t* us
                           const int32_t* target_rowptr, const int32_t* target_items,
                           int32_t n_splits, void* scratch, size_t scratch_bytes,
                           float* target_score, int32_t* rank, void* stream);
+
+/* ---- optimizer (main.py's torch.optim.Adam(model.parameters(), lr)) ------------------------- */
+/* One Adam step over up to LGCN_ADAM_MAX_TENSORS fp32 tensors in ONE launch, bit for bit what
+ * torch.optim.Adam with default arguments leaves on a HIP device (torch 2.10's
+ * _multi_tensor_adam, non-capturable branch: seven _foreach passes, every intermediate rounded
+ * to fp32). Per element, in fp32, fma = one rounding:
+ *     g' = fma(weight_decay, p, g)                       only if weight_decay != 0
+ *     m  = |w| < 0.5 ? fma(w, g' - m, m) : fma(-(1 - w), g' - m, g')        w = lerp_w (ATen lerp)
+ *     v  = fma(one_minus_beta2, g' * g', v * beta2)
+ *     t  = sqrt(v) / bc2_sqrt + eps                      IEEE sqrt and division, three roundings
+ *     p  = fma(step_size, m / t, p)                      IEEE division
+ * (DESIGN.md §5 "Optimizer" records how each rounding was settled against torch on the GPU.)
+ * The caller computes the scalars in double exactly as torch/optim/adam.py does:
+ *     lerp_w = 1 - beta1, one_minus_beta2 = 1 - beta2,
+ *     step_size = (lr / (1 - beta1 ** step)) * -1,  bc2_sqrt = (1 - beta2 ** step) ** 0.5
+ * (per tensor: step counts may differ); the library narrows each to float once, as ATen's opmath
+ * cast does.
+ * The table is read on the host during the call and travels to the kernel by value in its
+ * arguments: no copy, no synchronisation, nothing read back, capture-safe, on `stream`. A block
+ * takes one chunk of LGCN_ADAM_CHUNK consecutive elements of one tensor; a tensor whose four
+ * pointers are all 16-B aligned is accessed with 16-B loads and stores (scalar for the last
+ * n % 4 elements), any other tensor by element. Element counts and offsets are 64-bit.
+ * p, g, m and v of all tensors must not overlap (not checked).
+ * LGCN_EINVAL, before any HIP call: n_tensors outside [0, LGCN_ADAM_MAX_TENSORS]; with
+ * n_tensors > 0 a NULL table or NULL hyper, a non-finite hyper value, n < 0, bc2_sqrt not above
+ * 0, a NULL pointer in a tensor with n > 0, or more than 2^24 - 1 chunks in all (the grid).
+ * n_tensors == 0 or every n == 0 returns 0 without a launch; a tensor with n == 0 is skipped. */
+#define LGCN_ADAM_MAX_TENSORS 16
+#define LGCN_ADAM_CHUNK 4096       /* elements per block; a multiple of 1024 */
+typedef struct {
+    float* p;            /* parameter, updated in place */
+    const float* g;      /* gradient, read only */
+    float* m;            /* exp_avg, updated in place */
+    float* v;            /* exp_avg_sq, updated in place */
+    int64_t n;           /* elements */
+    double step_size;    /* (lr / bias_correction1) * -1 */
+    double bc2_sqrt;     /* bias_correction2 ** 0.5 */
+} lgcn_adam_tensor_t;
+typedef struct {
+    double lerp_w, beta2, one_minus_beta2, eps, weight_decay;
+} lgcn_adam_hyper_t;
+int     lgcn_adam_step(const lgcn_adam_tensor_t* tensors_host, int32_t n_tensors,
+                       const lgcn_adam_hyper_t* hyper, void* stream);
+/* host only: the blocks a tensor of n elements takes, ceil(n / LGCN_ADAM_CHUNK) (0 for n <= 0) */
+int64_t lgcn_adam_chunks(int64_t n);
 
 #ifdef __cplusplus
 }

@@ -76,7 +76,9 @@ class LightGCN_Fusion(nn.Module):
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
                   item_brand=None, brand_loss_weight=0.1):
         """One epoch of bpr_step batches over one device-side draw of the sampler
-        (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop."""
+        (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
+        `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
+        engine, with torch.optim.Adam's bits."""
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
                                brand_loss_weight=brand_loss_weight)
