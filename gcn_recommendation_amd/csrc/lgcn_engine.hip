@@ -466,6 +466,27 @@ int mean_empty(const int32_t* row_ids, int32_t n, const lgcn_epilogue_t& ep_in, 
     return dispatch_geo(g, f);
 }
 
+struct MeanSharedF {
+    const int32_t* rowptr; const lgcn_edge_t* edges; const int32_t* row_ids; const int32_t* rep;
+    int32_t n; const lgcn_rows_t* x; int32_t dW; const lgcn_epilogue_t* ep; float* y; int64_t ldy;
+    hipStream_t s;
+    template <typename V, int G, int NV> int operator()() const {
+        return launch_mean_shared_t<V, G, NV>(rowptr, edges, row_ids, rep, n, *x, dW, *ep, y, ldy,
+                                              s);
+    }
+};
+
+// the MEAN of n shared rows (k_mean_shared): slots of rowptr / row_ids / rep, X = layer K-1
+int mean_shared(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
+                const int32_t* rep, int32_t n, const lgcn_rows_t& x, const lgcn_epilogue_t& ep_in,
+                float* y, int64_t ldy, int32_t d, hipStream_t s) {
+    const lgcn_epilogue_t ep = with_pow2(ep_in);
+    const bool vec_ok = rows_aligned(x) && al16(y) && (ldy % 4 == 0) && epi_aligned(ep);
+    const Geo g = pick_geo(d, vec_ok);
+    MeanSharedF f{rowptr, edges, row_ids, rep, n, &x, g.dW, &ep, y, ldy, s};
+    return dispatch_geo(g, f);
+}
+
 lgcn_rows_t dense_rows(const float* p, int32_t n, int64_t ld) {
     lgcn_rows_t r;
     r.p0 = r.p1 = r.p2 = p;
@@ -1541,11 +1562,33 @@ struct LayerIO {
     lgcn_epilogue_t ep;
 };
 
+// Layer k of a K-layer forward: STORE into layer buffer k-1, the last one MEAN into `out`.
+LayerIO forward_io(int k, int32_t K, const lgcn_rows_t& emb, float* const* layer_bufs_host,
+                   float* out, int32_t n, int32_t d) {
+    LayerIO io;
+    memset(&io, 0, sizeof(io));
+    io.x = (k == 1) ? emb : dense_rows(layer_bufs_host[k - 2], n, d);
+    io.xdiv = 1.f;
+    if (k < K) {
+        io.ep.mode = LGCN_EPI_STORE;
+        io.y = layer_bufs_host[k - 1];
+    } else {
+        io.ep.mode = LGCN_EPI_MEAN;
+        io.ep.n_prev = K;
+        io.ep.div = (float)(K + 1);
+        io.ep.prev0 = emb;
+        for (int i = 0; i + 1 < K; ++i) io.ep.prev_dense[i] = layer_bufs_host[i];
+        io.ep.ld_prev = d;
+        io.y = out;
+    }
+    return io;
+}
+
 // Segment g of layer k: slots [lo, hi) under plans[2 * g + (k & 1)] on lane L.
 int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
               int32_t lo, int32_t hi, const lgcn_hub_plan_t* plans, int k, int g,
               const LayerIO& io, int32_t d, const lgcn_sched* sc, const Lane& L, Deps* dp,
-              int32_t empty_tail = 0) {
+              int32_t empty_tail = 0, int32_t shared_tail = 0, const int32_t* rep = nullptr) {
     if (empty_tail > 0) {
         // the segment's last slots hold rows without a record that no record references: the
         // launches end before them. A STORE leaves them unwritten (nothing gathers them); their
@@ -1554,11 +1597,38 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
         if (io.ep.mode == LGCN_EPI_MEAN)
             if (int e = mean_empty(row_ids + hi, empty_tail, io.ep, io.y, d, d, L.main)) return e;
     }
+    // the shared rows (lgcn_shared_t) sit before the empty ones: the launches end before them
+    // too. A STORE leaves them unwritten (every record that named them names their
+    // representative); their mean (k_mean_shared) needs what the segment's MEAN layer needs:
+    // side 1's layer K-1 with both walked parts (the lane's main stream has waited for them when
+    // the layer starts) and side 0's earlier layers (`late`).
+    hi -= shared_tail;
+    const bool has_shared = shared_tail > 0 && io.ep.mode == LGCN_EPI_MEAN;
+    auto shared_mean = [&](hipStream_t st) -> int {
+        if (!has_shared) return 0;
+        return mean_shared(rowptr + hi, edges, row_ids + hi, rep, shared_tail, io.x, io.ep, io.y,
+                           d, d, st);
+    };
+    // It runs beside the layer on the lane's part-1 stream — forked from the main stream where the
+    // layer starts (plus `late`), joined back after the layer: after the layer on the main stream
+    // it was the forward's last kernel, alone on the chip for 0.37 ms (C3, one box, alternating:
+    // 11.26-11.47 ms after, 11.07-11.17 ms beside). Under a restricted capture or
+    // without aux streams it follows the layer on the main stream.
+    hipStream_t side = nullptr;
+    if (has_shared && hi > lo && L.view && L.view->n_aux > 0 &&
+        !capture_restricted(L.main)) {
+        side = L.view->aux[L.view->n_aux > 1 ? 1 : 0];
+        if (int e = link(sc, L.main, side)) return e;
+        if (int e = wait_late(side, dp)) return e;
+        if (int e = shared_mean(side)) return e;
+    }
     if (hi <= lo) {  // nothing to run: the deferred parts are "done" here
         if (dp && dp->defer && sc)
             for (int i = 0; i < 2; ++i)
                 if (int e = record(sc, L.main, &dp->part_done[i])) return e;
-        return 0;
+        if (has_shared)
+            if (int e = wait_late(L.main, dp)) return e;
+        return shared_mean(L.main);
     }
     const int h = (k - 1) * kSegs + g;
     lgcn_sched v;
@@ -1584,7 +1654,8 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
     if (dq == &local)
         for (int i = 0; i < 2; ++i)
             if (int e = record(sc, L.main, &dp->part_done[i])) return e;
-    return 0;
+    if (side) return link(sc, side, L.main);
+    return shared_mean(L.main);
 }
 
 // The sided propagation (forward and backward): layer k of one side reads layer k-1 of the
@@ -1604,7 +1675,13 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
 int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
               const lgcn_sides_t& sd, const lgcn_hub_plan_t* plans, int32_t d, int32_t K,
               const std::function<LayerIO(int)>& layer, const lgcn_sched* sched, hipStream_t s,
-              const int32_t* empty_tail = nullptr) {
+              const int32_t* empty_tail = nullptr, const lgcn_shared_t* sh = nullptr) {
+    // shared rows (lgcn_shared_t): side 1 reads the re-pointed records from layer 2 on; `edges`
+    // and `row_ids` are the caller's edges_l1 and partitioned row ids
+    const lgcn_edge_t* edges_ln = sh ? sh->edges_ln : edges;
+    int32_t rep_off[kSegs] = {0, 0, 0, 0};
+    if (sh)
+        for (int g = 1; g < kSegs; ++g) rep_off[g] = rep_off[g - 1] + sh->shared_tail[g - 1];
     Lane lanes[2];
     bool l1_aux = false;
     if (sched) sched->pool->next = 0;
@@ -1646,8 +1723,8 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
                 dp.late_emu[0] = part[k - 1][0];
                 dp.late_emu[1] = part[k - 1][1];
             }
-            if (int e = seg_layer(rowptr, edges, row_ids, sd.split, n, plans, k, 3, io, d, sched,
-                                  L, &dp, empty_tail ? empty_tail[3] : 0))
+            if (int e = seg_layer(rowptr, k >= 2 ? edges_ln : edges, row_ids, sd.split, n, plans,
+                                  k, 3, io, d, sched, L, &dp, empty_tail ? empty_tail[3] : 0))
                 return e;
             if (k < K && sched) {
                 if (int e = record(sched, L.main, &rest[k])) return e;
@@ -1669,7 +1746,9 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
                 Deps dp;
                 if (mean && k >= 2) dp.late[0] = cls[k - 1][c];
                 if (int e = seg_layer(rowptr, edges, row_ids, lo[c], seg_hi(c, n), plans, k, c,
-                                      io, d, sched, L, &dp, empty_tail ? empty_tail[c] : 0))
+                                      io, d, sched, L, &dp, empty_tail ? empty_tail[c] : 0,
+                                      sh ? sh->shared_tail[c] : 0,
+                                      sh ? sh->rep + rep_off[c] : nullptr))
                     return e;
                 if (sched)
                     if (int e = record(sched, L.main, &cls[k][c])) return e;
@@ -1887,25 +1966,7 @@ int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* 
     hipStream_t s = S(stream);
     if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
     if (int e = check_sides(rowptr, row_ids, n, sides, plans)) return e;
-    auto layer = [&](int k) {
-        LayerIO io;
-        memset(&io, 0, sizeof(io));
-        io.x = (k == 1) ? emb : dense_rows(layer_bufs_host[k - 2], n, d);
-        io.xdiv = 1.f;
-        if (k < K) {
-            io.ep.mode = LGCN_EPI_STORE;
-            io.y = layer_bufs_host[k - 1];
-        } else {
-            io.ep.mode = LGCN_EPI_MEAN;
-            io.ep.n_prev = K;
-            io.ep.div = (float)(K + 1);
-            io.ep.prev0 = emb;
-            for (int i = 0; i + 1 < K; ++i) io.ep.prev_dense[i] = layer_bufs_host[i];
-            io.ep.ld_prev = d;
-            io.y = out;
-        }
-        return io;
-    };
+    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
     if (lean) {  // every tail inside its segment
         const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
         for (int g = 0; g < kSegs; ++g)
@@ -1914,6 +1975,39 @@ int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* 
     }
     return run_sides(rowptr, edges, row_ids, *sides, plans, d, K, layer, sched, s,
                      lean ? lean->empty_tail : nullptr);
+}
+
+int lgcn_propagate_forward_sides_shared(const int32_t* rowptr, const lgcn_sides_t* sides,
+                                        const lgcn_hub_plan_t* plans, const lgcn_shared_t* sh,
+                                        lgcn_rows_t emb, int32_t d, int32_t K,
+                                        float* const* layer_bufs_host, float* out,
+                                        const lgcn_sched_t* sched, void* stream) {
+    const int32_t n = sides ? sides->n : -1;
+    if (int e = valid_geom(n, d)) return e;
+    if (K < 0 || !out || !sh) return LGCN_EINVAL;
+    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
+    if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
+    hipStream_t s = S(stream);
+    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
+    if (int e = check_sides(rowptr, sh->row_ids, n, sides, plans)) return e;
+    // every pair of tails inside its segment; shared rows are side-0 rows and need their arrays
+    const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
+    bool any = false;
+    for (int g = 0; g < kSegs; ++g) {
+        const int32_t et = sh->empty_tail[g], st = sh->shared_tail[g];
+        if (et < 0 || st < 0 || (int64_t)et + st > b[g + 1] - b[g]) return LGCN_EINVAL;
+        any = any || st > 0;
+    }
+    if (sh->shared_tail[3] != 0) return LGCN_EINVAL;
+    // one side-0 segment only: a class's mean waits for its own class's layer K-1 alone, and a
+    // representative in another class would be read without a wait
+    if ((sh->shared_tail[0] > 0) + (sh->shared_tail[1] > 0) + (sh->shared_tail[2] > 0) > 1)
+        return LGCN_EINVAL;
+    if (any && (!sh->row_ids || !sh->edges_l1 || !sh->edges_ln || !sh->rep)) return LGCN_EINVAL;
+    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
+    // K = 1 has no intermediate layer to share: the lean forward over the partitioned slots
+    return run_sides(rowptr, sh->edges_l1, sh->row_ids, *sides, plans, d, K, layer, sched, s,
+                     sh->empty_tail, K >= 2 && any ? sh : nullptr);
 }
 
 int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,

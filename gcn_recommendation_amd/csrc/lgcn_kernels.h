@@ -655,6 +655,43 @@ __global__ __launch_bounds__(kBlock) void k_mean_empty(const int32_t* __restrict
     }
 }
 
+// The MEAN output of the shared rows (lgcn_shared_t: slots [0, n_rows) of row_ids / rowptr / rep,
+// one record each): row u's layers 1..K-1 are those of its representative r = rep[slot], bit for
+// bit, and its layer K is the one-edge chain fma(w, X[p], +0) of its record (p, w), so
+// out[u] = ((((+0 + E0[u]) + L_1[r]) + ... + L_{K-1}[r]) + fma(w, X[p], +0)) / (K+1) — the order,
+// the +0 start and the division of epilogue_store<MEAN>. Writes out[u] only.
+template <typename V, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_mean_shared(const int32_t* __restrict__ rowptr,
+                                                        const lgcn_edge_t* __restrict__ edges,
+                                                        const int32_t* __restrict__ row_ids,
+                                                        const int32_t* __restrict__ rep,
+                                                        int32_t n_rows, lgcn_rows_t x, int32_t dW,
+                                                        lgcn_epilogue_t ep, float* __restrict__ y,
+                                                        int64_t ldy) {
+    using T = VT<V>;
+    constexpr int RPB = kBlock / G;
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t slot = (int64_t)blockIdx.x * RPB + threadIdx.x / G;
+    if (slot >= n_rows) return;
+    const int32_t row = row_ids[slot];
+    const int32_t r = rep[slot];
+    const int2 e = load_edge(edges + rowptr[slot]);
+    const float w = __int_as_float(e.y);
+    const float* xp = seg_row(x, e.x);
+    const float* e0 = seg_row(ep.prev0, row);
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const int c = lane + q * G;
+        if (c >= dW) continue;
+        const V acc = T::fma(w, T::load(xp + c * T::W), T::zero());
+        V s = T::add(T::zero(), load_stream<V>(e0 + c * T::W));
+        for (int i = 0; i + 1 < ep.n_prev; ++i)
+            s = T::add(s, T::load(ep.prev_dense[i] + (int64_t)r * ep.ld_prev + c * T::W));
+        s = T::add(s, acc);
+        store_out<V>(y + (int64_t)row * ldy + c * T::W, div_exact<V>(s, ep.div, ep.pad));
+    }
+}
+
 // Row-sparsity mask of a block: bit r of mask = row r holds a value != 0 (NaN counts). A block
 // owns 256 rows = 8 mask words (plain stores, no global atomics); one atomicAdd per block
 // accumulates the live-row count.
@@ -882,6 +919,18 @@ int launch_mean_empty_t(const int32_t* row_ids, int32_t n_rows, const lgcn_rows_
     if (grid == 0) return 0;
     hipLaunchKernelGGL((k_mean_empty<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, row_ids,
                        n_rows, e0, dW, div, inv_bits, y, ldy);
+    return last_err();
+}
+
+template <typename V, int G, int NV>
+int launch_mean_shared_t(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
+                         const int32_t* rep, int32_t n_rows, const lgcn_rows_t& x, int32_t dW,
+                         const lgcn_epilogue_t& ep, float* y, int64_t ldy, hipStream_t s) {
+    constexpr int RPB = kBlock / G;
+    const int64_t grid = ((int64_t)n_rows + RPB - 1) / RPB;
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL((k_mean_shared<V, G, NV>), dim3((uint32_t)grid), dim3(kBlock), 0, s, rowptr,
+                       edges, row_ids, rep, n_rows, x, dW, ep, y, ldy);
     return last_err();
 }
 

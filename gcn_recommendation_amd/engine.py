@@ -155,6 +155,13 @@ class LeanT(ctypes.Structure):
     _fields_ = [("empty_tail", ctypes.c_int32 * 4)]
 
 
+class SharedT(ctypes.Structure):
+    """lgcn_shared_t"""
+    _fields_ = [("empty_tail", ctypes.c_int32 * 4), ("shared_tail", ctypes.c_int32 * 4),
+                ("row_ids", ctypes.c_void_p), ("edges_l1", ctypes.c_void_p),
+                ("edges_ln", ctypes.c_void_p), ("rep", ctypes.c_void_p)]
+
+
 class AdamTensorT(ctypes.Structure):
     """lgcn_adam_tensor_t"""
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p),
@@ -277,6 +284,10 @@ ABI = [
                                                          ctypes.POINTER(PlanT),
                                                          ctypes.POINTER(LeanT), RowsT, _I32, _I32,
                                                          _P, _P, _P, _P]),
+    ("lgcn_propagate_forward_sides_shared", ctypes.c_int, [_P, ctypes.POINTER(SidesT),
+                                                           ctypes.POINTER(PlanT),
+                                                           ctypes.POINTER(SharedT), RowsT, _I32,
+                                                           _I32, _P, _P, _P, _P]),
     ("lgcn_propagate_backward_sides", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(SidesT),
                                                      ctypes.POINTER(PlanT), RowsT, _P, _I32, _I32,
                                                      _P, _P, _P, _P]),
@@ -668,6 +679,7 @@ class Graph:
         self._rowptr_host = None
         self._row_ids_host = None
         self._lean = None
+        self._shared = None
 
     def rowptr_host(self):
         """Row pointers in storage order (slots when degree-ordered)."""
@@ -741,6 +753,23 @@ class Graph:
                                    self.segments())
         return self._lean
 
+    def shared(self):
+        """The SharedPlan of this side-major graph (cached with it, as lean())."""
+        if self._shared is None:
+            self._shared = shared_plan(self.rowptr, self.edges, self.row_ids, self.split,
+                                       self.segments(), self.lean())
+        return self._shared
+
+    @property
+    def n_shared(self):
+        """Side-0 rows whose layer rows their group's representative stands for (shared())."""
+        return self.shared().n_shared
+
+    @property
+    def n_groups(self):
+        """Groups (p, value bits of w) among the single-record derived rows (shared())."""
+        return self.shared().n_groups
+
     @property
     def n_empty(self):
         """Rows in the `empty` mask of lean()."""
@@ -778,7 +807,7 @@ class LeanPlan:
                every layer of it but E0 is +0 and nothing gathers it;
       derived: a side-0 row with exactly one stored record (p, w), every stored record naming it
                as its column lying in row p with w's value bits — its layer-k row is
-               fma(w, E_{k-1}[p], +0), which row p can form itself. No kernel uses this mask yet.
+               fma(w, E_{k-1}[p], +0), which row p can form itself. shared_plan starts from it.
     empty_tail[g]: the trailing slots of segment g (Graph.segments()) whose rows are all `empty`
     — what lgcn_propagate_forward_sides_lean takes."""
 
@@ -832,6 +861,118 @@ def lean_plan(rowptr, edges, row_ids, split, segments):
         tails.append(int(b - a - (int(live[-1]) + 1 if live.numel() else 0)))
     return LeanPlan(_bitmask(empty), _bitmask(derived), int(empty.sum()), int(derived.sum()),
                     tails)
+
+
+def _unmask(words, n):
+    """Row flags (bool [n]) of a bitmask in lgcn_rows_nonzero's format (_bitmask's inverse)."""
+    sh = torch.arange(32, dtype=torch.int64, device=words.device)
+    return (((words.long().unsqueeze(1) >> sh) & 1).reshape(-1)[:n]).bool()
+
+
+class SharedPlan:
+    """One layer row per group of single-record side-0 rows (lgcn_shared_t). The
+    derived rows of a LeanPlan with equal record (p, value bits of w) hold bit-identical rows in
+    every layer k >= 1; the member in the lowest slot is the group's representative, every other
+    member is shared: no intermediate layer row of it is written, gathered or read.
+      row_ids_s: the graph's row ids, side 0's single-record slots stably partitioned — the
+                 shared rows last, directly before the segment's empty tail;
+      edges_l1:  the graph's records with those slots' records moved the same way;
+      edges_ln:  edges_l1 with every column naming a shared row re-pointed to its representative
+                 (record positions and value bits unchanged);
+      shared_tail[g]: shared slots of segment g; rep: their representatives' row ids (int32, in
+                 slot order); tail_slots[g]: their slot range.
+    Sharing is off (every tail 0, the graph's own arrays) when side 0 runs as more than one
+    segment (LGCN_CLASSES=1: a class's mean waits only for its own class, and a representative
+    may lie in another), and in a segment whose single-record slots do not end at its empty
+    tail."""
+
+    def __init__(self, row_ids_s, edges_l1, edges_ln, rep, empty_tail, shared_tail, tail_slots,
+                 n_shared, n_groups):
+        self.row_ids_s, self.edges_l1, self.edges_ln, self.rep = row_ids_s, edges_l1, edges_ln, rep
+        self.empty_tail, self.shared_tail = tuple(empty_tail), tuple(shared_tail)
+        self.tail_slots = tuple(tail_slots)
+        self.n_shared, self.n_groups = n_shared, n_groups
+
+    def shared_rows(self):
+        """Row ids (int64) of the shared rows, in slot order."""
+        return torch.cat([self.row_ids_s[a:b] for a, b in self.tail_slots]).long()
+
+    def struct(self):
+        st = SharedT()
+        for g in range(N_SEGS):
+            st.empty_tail[g], st.shared_tail[g] = self.empty_tail[g], self.shared_tail[g]
+        st.row_ids, st.edges_l1 = self.row_ids_s.data_ptr(), self.edges_l1.data_ptr()
+        st.edges_ln, st.rep = self.edges_ln.data_ptr(), self.rep.data_ptr()
+        return st
+
+
+def shared_plan(rowptr, edges, row_ids, split, segments, lean):
+    """SharedPlan of a CSR in side-major slots under its LeanPlan `lean` (arguments as
+    lean_plan's; torch ops only, so it runs on CPU tensors too). Neither rowptr, edges nor
+    row_ids is modified."""
+    dev = rowptr.device
+    n = rowptr.numel() - 1
+    nnz = int(rowptr[-1])
+    ids = row_ids.long()
+    i64 = dict(dtype=torch.int64, device=dev)
+    tails, tail_slots = [0] * N_SEGS, [(b, b) for _, b in segments]
+    none = SharedPlan(row_ids, edges, edges, torch.zeros(0, dtype=torch.int32, device=dev),
+                      lean.empty_tail, tails, tail_slots, 0, 0)
+    side0 = [g for g, (a, b) in enumerate(segments[:3]) if b > a]
+    if len(side0) != 1 or nnz == 0:
+        return none
+    g = side0[0]
+    a, b = segments[g]
+    deg = (rowptr[a + 1:b + 1] - rowptr[a:b]).long()
+    one = torch.nonzero(deg == 1).flatten()
+    if one.numel() == 0:
+        return none
+    s0, s1 = a + int(one[0]), a + int(one[-1]) + 1
+    if s1 - s0 != one.numel() or s1 != b - lean.empty_tail[g]:
+        return none
+    m = s1 - s0
+    pos = rowptr[s0:s1].long()  # (consecutive: one record per slot)
+    rec = edges[pos]
+    # groups: the candidates sorted stably by their record, so a run's first entry is the
+    # group's member in the lowest slot
+    ci = torch.nonzero(_unmask(lean.derived, n)[ids[s0:s1]]).flatten()
+    if ci.numel() == 0:
+        return none
+    keys, perm = torch.sort(rec[ci], stable=True)
+    first = torch.ones_like(keys, dtype=torch.bool)
+    first[1:] = keys[1:] != keys[:-1]
+    at = torch.arange(keys.numel(), **i64)
+    start = torch.cummax(torch.where(first, at, torch.zeros_like(at)), 0).values
+    rep_slot = torch.full((m,), -1, **i64)   # by slot - s0: the representative's slot - s0
+    rep_slot[ci[perm[~first]]] = ci[perm[start]][~first]
+    is_shared = rep_slot >= 0
+    sh = torch.nonzero(is_shared).flatten()
+    n_groups, n_shared = int(first.sum()), int(sh.numel())
+    if n_shared == 0:
+        none.n_groups = n_groups
+        return none
+    order = torch.cat([torch.nonzero(~is_shared).flatten(), sh])  # the stable partition
+    row_ids_s = row_ids.clone()
+    row_ids_s[s0:s1] = row_ids[s0:s1][order]
+    edges_l1 = edges.clone()
+    edges_l1[pos] = rec[order]
+    rep_rows = ids[s0 + rep_slot[sh]]
+    new_id = torch.arange(n, **i64)
+    new_id[ids[s0 + sh]] = rep_rows
+    edges_ln = edges_l1.clone()
+    r = edges_l1[:nnz]
+    edges_ln[:nnz] = ((r >> 32) << 32) | new_id[r & 0xffffffff]
+    tails[g] = n_shared
+    tail_slots[g] = (s1 - n_shared, s1)
+    return SharedPlan(row_ids_s, edges_l1, edges_ln, rep_rows.to(torch.int32), lean.empty_tail,
+                      tails, tail_slots, n_shared, n_groups)
+
+
+def share_enabled():
+    """Whether propagate_forward(share=None) shares rows: on unless LGCN_SHARE=0 (same bits). The
+    variable is how bench.py, which passes no `share`, measures the forward without the path
+    (DESIGN §8 "Shared rows")."""
+    return os.environ.get("LGCN_SHARE", "1") != "0"
 
 
 def slot_key_enabled(g):
@@ -1446,7 +1587,7 @@ def alloc_layers(n, d, count, device):
 
 def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
                       return_layers=False, hub_mode=None, emu_min=None, kernel_events=None,
-                      lean=None):
+                      lean=None, share=None):
     """final = mean(E0, Â E0, ..., Â^K E0) with E0 = cat(segments) (never materialised).
 
     layer_events: optional list of (start, end) torch.cuda.Event pairs recorded on the current
@@ -1459,6 +1600,12 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
     on when the layers are private to the call (no return_layers); True with return_layers hands
     back layers whose skipped rows hold whatever the buffers held. No effect on the one-operator
     schedule.
+    share: the lean forward with one layer row per group of single-record side-0 rows
+    (SharedPlan: the shared rows of the layer buffers stay unwritten too; same final bits; the
+    plan keeps two more edge arrays on the device). None: on exactly when lean is on and the
+    layers are private to the call (env LGCN_SHARE=0, share_enabled: off); True with
+    return_layers hands back layers whose shared rows hold whatever the buffers held;
+    False runs the lean path alone. No effect at K <= 1 or on the one-operator schedule.
     """
     if hub_threshold is None:
         hub_threshold = hub_threshold_from_env()
@@ -1481,9 +1628,18 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
             return (out, []) if return_layers else out
         layers = alloc_layers(n, d, K - 1, dev)
         if use_sides(graph, layer_events, kernel_events):
+            if share is None:
+                share = lean is not False and not return_layers and share_enabled()
             if lean is None:
-                lean = not return_layers
+                lean = share or not return_layers
+            if share and not lean:
+                raise LgcnError("share=True needs lean: the shared rows sit before the empty tail")
             lp = graph.lean().struct() if lean else None
+            # (K = 1 has no intermediate layer; rows of one record are bundle rows from a hub
+            # threshold of 1 on)
+            sp = graph.shared() if share and K >= 2 and hub_threshold >= 1 else None
+            if sp is not None and sp.n_shared == 0:
+                sp = None
             plans, _ = _side_plans(graph, d, hub_threshold, hub_mode, emu_min,
                                    _aligned16(segments))
             sc = sched_for(dev)
@@ -1491,12 +1647,19 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
             bufs = (ctypes.c_void_p * max(K - 1, 1))(*[t.data_ptr() for t in layers])
             sides = graph.sides_struct()
             try:
-                _check(lib.lgcn_propagate_forward_sides_lean(
-                    _ptr(graph.rowptr), _ptr(graph.edges), _ptr(graph.row_ids),
-                    ctypes.byref(sides), plans, ctypes.byref(lp) if lp is not None else None,
-                    e0, d, K, bufs, _ptr(out),
-                    sc.handle if sc is not None else None, stream),
-                    "lgcn_propagate_forward_sides_lean")
+                if sp is not None:
+                    st = sp.struct()
+                    _check(lib.lgcn_propagate_forward_sides_shared(
+                        _ptr(graph.rowptr), ctypes.byref(sides), plans, ctypes.byref(st), e0, d, K,
+                        bufs, _ptr(out), sc.handle if sc is not None else None, stream),
+                        "lgcn_propagate_forward_sides_shared")
+                else:
+                    _check(lib.lgcn_propagate_forward_sides_lean(
+                        _ptr(graph.rowptr), _ptr(graph.edges), _ptr(graph.row_ids),
+                        ctypes.byref(sides), plans, ctypes.byref(lp) if lp is not None else None,
+                        e0, d, K, bufs, _ptr(out),
+                        sc.handle if sc is not None else None, stream),
+                        "lgcn_propagate_forward_sides_lean")
             finally:
                 ev.clear()
             _note_schedule(sc, graph)

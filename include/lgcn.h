@@ -650,6 +650,40 @@ int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* 
                                       lgcn_rows_t emb, int32_t d, int32_t K,
                                       float* const* layer_bufs_host, float* out,
                                       const lgcn_sched_t* sched, void* stream);
+/* The lean forward with one layer row per group of single-record side-0 rows. Side-0
+ * rows with exactly one stored record (p, w) and equal (p, value bits of w) hold bit-identical
+ * rows fma(w, E_{k-1}[p], +0) in every layer k >= 1, so the member in the lowest slot (the
+ * representative) stands for its group and the others ("shared" rows) are never materialised:
+ *  - row_ids: the graph's row ids with side 0's single-record slots stably partitioned, the
+ *    shared rows last — the shared_tail[g] slots directly before segment g's empty_tail[g] (all
+ *    these slots hold one record, so rowptr and every hub plan stay as they are);
+ *  - edges_l1: the graph's records with those slots' records moved the same way — what side 0
+ *    reads in every layer and side 1 in layer 1 (E0 rows are parameters: all different);
+ *  - edges_ln: edges_l1 with every column that names a shared row re-pointed to its
+ *    representative (positions and value bits unchanged: every chain multiplies the same values
+ *    with bit-identical rows in the same order) — what side 1 reads in layers k >= 2;
+ *  - rep[t]: the representative's row id of shared slot t, in slot order over the segments.
+ * Every half-layer launch of segment g ends before shared_tail[g] + empty_tail[g]; the STORE
+ * layers leave the shared rows of layer_bufs_host UNWRITTEN, and after the segment's MEAN layer
+ * one kernel writes out[u] = (((+0 + E0[u]) + L_1[r]) + ... + L_{K-1}[r] + fma(w, L_{K-1}[p], +0))
+ * / (K+1) for every shared row u with representative r: epilogue_store's order, the reference's
+ * bits. K <= 1 has no intermediate layer: it runs as the lean forward over row_ids / edges_l1.
+ * LGCN_EINVAL before any launch: a negative tail or tails that do not fit their segment, a NULL
+ * pointer beside a nonzero tail, shared rows on side 1 (shared_tail[3] != 0), shared rows in
+ * more than one of side 0's segments (a class's mean waits for its own class's earlier layers
+ * only, and a representative may lie in another class: sharing needs side 0 as one segment). */
+typedef struct {
+    int32_t empty_tail[4], shared_tail[4];
+    const int32_t* row_ids;
+    const lgcn_edge_t* edges_l1;
+    const lgcn_edge_t* edges_ln;
+    const int32_t* rep;
+} lgcn_shared_t;
+int lgcn_propagate_forward_sides_shared(const int32_t* rowptr, const lgcn_sides_t* sides,
+                                        const lgcn_hub_plan_t* plans, const lgcn_shared_t* shared,
+                                        lgcn_rows_t emb, int32_t d, int32_t K,
+                                        float* const* layer_bufs_host, float* out,
+                                        const lgcn_sched_t* sched, void* stream);
 int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,
                                   const int32_t* row_ids, const lgcn_sides_t* sides,
                                   const lgcn_hub_plan_t* plans, lgcn_rows_t grad_out,
