@@ -1112,28 +1112,37 @@ struct EventPool {
     int next = 0;
     int32_t state[5] = {0, 0, 0, 0, 0};  // the latest call's schedule (lgcn_sched_state)
 };
+// the streams one layer's emulated parts and chain rows run on beside its layer kernel
+struct StreamSet {
+    hipStream_t aux[3];
+    int n_aux;
+};
+// optional events of one layer under a stream set: t0 / t1 recorded around the layer kernel,
+// trace [8] at its phases (all NULL without a stream set)
+struct Marks {
+    hipEvent_t t0, t1;
+    hipEvent_t* trace;
+};
 }  // namespace
 
 struct lgcn_sched {
-    hipStream_t aux[3];
-    int n_aux;
-    EventPool* pool;        // owned by the root schedule; lane 1's view shares it
+    StreamSet lane0;        // the caller's lane (and every one-operator layer)
+    EventPool* pool;
     int32_t slots[2];       // walk LDS slots of part 0 / part 1 (0 = default)
     int chain;              // 0: chain rows are walked too (tests / A-B)
-    hipEvent_t t0, t1;      // optional: recorded on the caller's stream around the layer kernel
-    hipEvent_t* trace;      // optional [8]: phase events (LGCN_SCHED_TRACE)
+    Marks marks;            // LGCN_SCHED_TIMING_START / _END / LGCN_SCHED_TRACE (lgcn_layer)
     // bipartite lanes (lgcn_propagate_*_sides; created with >= 4 aux streams): the second lane's
-    // main stream and its own view (aux streams)
+    // main stream and its own aux streams
     hipStream_t lane1_main;
-    lgcn_sched* lane1;
+    StreamSet lane1;
     hipEvent_t* trace_sides;   // optional [32 K] (LGCN_SCHED_TRACE_SIDES)
     hipEvent_t* timing_sides;  // optional [8 K] (LGCN_SCHED_TIMING_SIDES)
     int classes;               // LGCN_SCHED_CLASSES (default 1)
     int lk_normal;             // LGCN_SCHED_LK_NORMAL (default 1)
     // LGCN_SCHED_LANE1_SHARED: lane 1 on the caller's stream and lane 0's aux streams in reverse
-    // order (lane1s: that view), so each of lane 1's streams is one of lane 0's
+    // order (lane0_rev), so each of lane 1's streams is one of lane 0's
     int lane1_shared;
-    lgcn_sched* lane1s;
+    StreamSet lane0_rev;
 };
 
 namespace {
@@ -1241,7 +1250,9 @@ bool chain_ok(const lgcn_rows_t& x, int32_t d) {
 int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
                int32_t n, const lgcn_hub_plan_t& p, const lgcn_rows_t& x, float xdiv,
                const uint32_t* x_nz, float* y, int64_t ldy, int32_t d, const lgcn_epilogue_t& ep,
-               const lgcn_sched* sc, hipStream_t s, Deps* dp = nullptr) {
+               const lgcn_sched* root, const StreamSet* ss, const Marks& mk, hipStream_t s,
+               Deps* dp = nullptr) {
+    const lgcn_sched* sc = ss ? root : nullptr;  // (its pool, slots and chain; streams: ss)
     const int32_t ne = p.n_emu_rows;
     // row-sparse X (the backward's first layer on a BPR batch): every emulated row is a chain
     // over its live edges (lgcn_live_rows) — no block pass, no walk
@@ -1250,7 +1261,7 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
     // walked rows read the block-pass scratch, which must cover their blocks
     if ((chains || live ? p.emu_part_blocks[1] : p.n_emu_blocks) > p.emu_scratch_blocks)
         return LGCN_EINVAL;
-    hipEvent_t* tr = sc ? sc->trace : nullptr;
+    hipEvent_t* tr = mk.trace;
     auto mark = [&](int k, hipStream_t st) -> int {
         return tr && tr[k] ? herr(hipEventRecord(tr[k], st)) : 0;
     };
@@ -1260,13 +1271,13 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
                               {p.emu_part_rows[1], ne, p.emu_part_blocks[1], p.n_emu_blocks}};
     const int slots[3] = {sc ? sc->slots[0] : 0, sc ? sc->slots[1] : 0, sc ? sc->slots[1] : 0};
     auto layer_kernel = [&](hipStream_t st) -> int {
-        if (sc && sc->t0)
-            if (int e = herr(hipEventRecord(sc->t0, st))) return e;
+        if (mk.t0)
+            if (int e = herr(hipEventRecord(mk.t0, st))) return e;
         if (int e = spmm_layer(rowptr, edges, row_ids, n, p.threshold, p.items, p.n_items,
                                p.partials, x, y, ldy, d, ep, xdiv, x_nz, st))
             return e;
-        if (sc && sc->t1)
-            if (int e = herr(hipEventRecord(sc->t1, st))) return e;
+        if (mk.t1)
+            if (int e = herr(hipEventRecord(mk.t1, st))) return e;
         return hub_combine(p.rows, p.n_rows, p.n_pre, p.partials, y, ldy, d, ep, st);
     };
     // a MEAN whose operands arrive late (the other lane's layer K-1) with an emu_out scratch: the
@@ -1318,8 +1329,8 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
         // beside the walks rather than before them (a dense G keeps every walked row walked and
         // makes every chain row a chain over all its edges: round 5, the dense backward's first
         // layer no longer waits for its chains before its walks start)
-        const int na = sc->n_aux;
-        hipStream_t a0 = sc->aux[0], a1 = sc->aux[na > 1 ? 1 : 0], a2 = sc->aux[na > 2 ? 2 : 0];
+        const int na = ss->n_aux;
+        hipStream_t a0 = ss->aux[0], a1 = ss->aux[na > 1 ? 1 : 0], a2 = ss->aux[na > 2 ? 2 : 0];
         if (int e = mark(0, s)) return e;
         if (int e = link(sc, s, a0)) return e;
         if (int e = lgcn_detail::live_prepare(edges, p.emu_blocks, p.n_emu_blocks, p.emu_rows, ne,
@@ -1370,15 +1381,15 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
         return done_on_s();
     }
     // fork: X is ready on `s` (parts 0 / 1 with a stream of their own: once their part_wait fires)
-    const int na = sc->n_aux;
+    const int na = ss->n_aux;
     const bool own = dp && na >= 3;
-    auto aux_of = [&](int part) { return sc->aux[part < na ? part : na - 1]; };
+    auto aux_of = [&](int part) { return ss->aux[part < na ? part : na - 1]; };
     if (int e = mark(0, s)) return e;
     hipEvent_t fork;
     if (int e = record(sc, s, &fork)) return e;
     for (int i = 0; i < na; ++i) {
         const hipEvent_t w = own && i < 2 && dp->part_wait[i] ? dp->part_wait[i] : fork;
-        if (int e = wait_ev(sc->aux[i], w)) return e;
+        if (int e = wait_ev(ss->aux[i], w)) return e;
     }
     // block passes first (the walk of part 0 starts as soon as its own is done), then the layer
     // kernel, then the walks and the chains
@@ -1395,7 +1406,7 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
     if (int e = wait_late(s, dp, !defer_epi)) return e;
     if (!defer_epi)
         for (int i = 0; i < na; ++i)
-            if (int e = wait_late(sc->aux[i], dp)) return e;
+            if (int e = wait_late(ss->aux[i], dp)) return e;
     // the layer kernel waits for part 0's block pass (round 5: the mean half-layers without this
     // wait measured the same, 12.40 / 12.68 vs 12.38 / 12.64 ms)
     if (parts[0].b1 > parts[0].b0)
@@ -1423,8 +1434,8 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
     // join: every row of Y written before `s` goes on — except deferred parts 0 and 1
     for (int i = 0; i < na; ++i) {
         if (own && dp->defer && i < 2) {
-            if (int e = record(sc, sc->aux[i], &dp->part_done[i])) return e;
-        } else if (int e = link(sc, sc->aux[i], s)) {
+            if (int e = record(sc, ss->aux[i], &dp->part_done[i])) return e;
+        } else if (int e = link(sc, ss->aux[i], s)) {
             return e;
         }
     }
@@ -1438,10 +1449,10 @@ int plan_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
 }
 
 // The bipartite schedule (lgcn_propagate_*_sides): a lane = the stream its half-layers' layer
-// kernels run on + the schedule view whose aux streams take their emulated / chain rows.
+// kernels run on + the stream set that takes their emulated / chain rows (NULL: its main stream).
 struct Lane {
     hipStream_t main;
-    const lgcn_sched* view;
+    const StreamSet* ss;
 };
 
 bool capturing(hipStream_t s) {
@@ -1470,10 +1481,10 @@ bool runtime_captures_full() {
 bool capture_restricted(hipStream_t s) { return capturing(s) && !runtime_captures_full(); }
 
 bool make_lanes(const lgcn_sched* sc, hipStream_t s, Lane lanes[2], bool& l1_aux) {
-    lanes[0] = Lane{s, sc};
-    const bool shared = sc && sc->lane1_shared && sc->lane1s;
-    const bool two = sc && (sc->lane1 || shared);
-    const lgcn_sched* l1v = shared ? sc->lane1s : (sc ? sc->lane1 : nullptr);
+    lanes[0] = Lane{s, sc ? &sc->lane0 : nullptr};
+    const bool shared = sc && sc->lane1_shared;
+    const bool two = sc && (sc->lane1_main || shared);
+    const StreamSet* l1v = shared ? &sc->lane0_rev : (sc ? &sc->lane1 : nullptr);
     const bool cap = capturing(s);
     l1_aux = two && l1v->n_aux > 0 && !(cap && !runtime_captures_full());
     lanes[1] = two ? Lane{shared ? s : sc->lane1_main, l1_aux ? l1v : nullptr} : lanes[0];
@@ -1492,8 +1503,8 @@ int fork_lanes(const lgcn_sched* sc, bool two, const Lane& l1, hipStream_t s) {
     hipEvent_t f;
     if (int e = record(sc, s, &f)) return e;
     if (int e = wait_ev(l1.main, f)) return e;
-    for (int i = 0; i < (l1.view ? l1.view->n_aux : 0); ++i)
-        if (int e = wait_ev(l1.view->aux[i], f)) return e;
+    for (int i = 0; i < (l1.ss ? l1.ss->n_aux : 0); ++i)
+        if (int e = wait_ev(l1.ss->aux[i], f)) return e;
     return 0;
 }
 
@@ -1502,8 +1513,8 @@ int fork_lanes(const lgcn_sched* sc, bool two, const Lane& l1, hipStream_t s) {
 int join_lanes(const lgcn_sched* sc, bool two, const Lane& l1, hipStream_t s) {
     if (!two) return 0;
     if (int e = link(sc, l1.main, s)) return e;
-    for (int i = 0; i < (l1.view ? l1.view->n_aux : 0); ++i)
-        if (int e = link(sc, l1.view->aux[i], s)) return e;
+    for (int i = 0; i < (l1.ss ? l1.ss->n_aux : 0); ++i)
+        if (int e = link(sc, l1.ss->aux[i], s)) return e;
     return 0;
 }
 
@@ -1584,11 +1595,70 @@ LayerIO forward_io(int k, int32_t K, const lgcn_rows_t& emb, float* const* layer
     return io;
 }
 
-// Segment g of layer k: slots [lo, hi) under plans[2 * g + (k & 1)] on lane L.
-int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
+// Layer k of a K-layer backward, Horner: h = G/(K+1) + Âᵀ h into grad_e0 or work_h alternately.
+// MeanBackward hands every layer c = G / (K+1); it is never materialised: layer 1 gathers
+// G / (K+1) on load and every epilogue adds G[row] / (K+1) (same rounding as c).
+LayerIO backward_io(int k, int32_t K, const lgcn_rows_t& grad_out, const uint32_t* grad_nz,
+                    float* work_h, float* grad_e0, int32_t n, int32_t d) {
+    auto out_of = [&](int j) { return ((K - j) % 2 == 0) ? grad_e0 : work_h; };
+    LayerIO io;
+    memset(&io, 0, sizeof(io));
+    io.x = k == 1 ? grad_out : dense_rows(out_of(k - 1), n, d);
+    io.xdiv = k == 1 ? (float)(K + 1) : 1.f;
+    io.x_nz = k == 1 ? grad_nz : nullptr;
+    io.y = out_of(k);
+    io.ep.mode = LGCN_EPI_ADD;
+    io.ep.addend = grad_out;
+    io.ep.addend_nz = grad_nz;
+    io.ep.div = (float)(K + 1);
+    return io;
+}
+
+// What every lgcn_propagate_* entry point checks first, in this order, and the K = 0 shortcut
+// y = x / 1 (`mean`: (+0 + x) / 1, the forward's mean(stack([E0]))). True: the call ends here
+// with *rc.
+bool prologue(int32_t n, int32_t d, int32_t K, bool ptrs_ok, const void* bufs,
+              const lgcn_rows_t& x, float* y, bool mean, hipStream_t s, int* rc) {
+    auto end = [&](int code) { *rc = code; return true; };
+    if (int e = valid_geom(n, d)) return end(e);
+    if (K < 0 || !ptrs_ok) return end(LGCN_EINVAL);
+    if (K > LGCN_MAX_LAYERS) return end(LGCN_ETOOMANY);  // 18 stacked layers: not ATen's order
+    if (K > 1 && !bufs) return end(LGCN_EINVAL);
+    if (K == 0) return end(scale_rows(x, n, d, 1.0f, y, d, s, mean));
+    return false;
+}
+
+// One layer after the other under one plan (lgcn_propagate_forward / _backward); ev_host: NULL
+// or 2 K events recorded around each layer.
+int run_layers(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids, int32_t n,
+               const lgcn_hub_plan_t* plan, int32_t d, int32_t K,
+               const std::function<LayerIO(int)>& layer, void* const* ev_host,
+               const lgcn_sched* sched, hipStream_t s) {
+    if (int e = check_plan(plan)) return e;
+    if (sched) sched->pool->next = 0;
+    for (int k = 1; k <= K; ++k) {
+        const LayerIO io = layer(k);
+        if (ev_host)
+            if (int e = herr(hipEventRecord((hipEvent_t)ev_host[2 * (k - 1)], s))) return e;
+        if (int e = plan_layer(rowptr, edges, row_ids, n, *plan, io.x, io.xdiv, io.x_nz, io.y, d, d,
+                               io.ep, sched, sched ? &sched->lane0 : nullptr,
+                               sched ? sched->marks : Marks{}, s))
+            return e;
+        if (ev_host)
+            if (int e = herr(hipEventRecord((hipEvent_t)ev_host[2 * (k - 1) + 1], s))) return e;
+    }
+    return 0;
+}
+
+// Segment g of layer k: slots [lo, hi) under plans[2 * g + (k & 1)] on lane L; `edges`: sr's
+// records this half-layer reads.
+int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const lgcn_shared_t& sr,
               int32_t lo, int32_t hi, const lgcn_hub_plan_t* plans, int k, int g,
-              const LayerIO& io, int32_t d, const lgcn_sched* sc, const Lane& L, Deps* dp,
-              int32_t empty_tail = 0, int32_t shared_tail = 0, const int32_t* rep = nullptr) {
+              const LayerIO& io, int32_t d, const lgcn_sched* sc, const Lane& L, Deps* dp) {
+    const int32_t* row_ids = sr.row_ids;
+    const int32_t empty_tail = sr.empty_tail[g], shared_tail = sr.shared_tail[g];
+    const int32_t* rep = sr.rep;  // (of this segment's shared rows: after the earlier segments')
+    for (int j = 0; j < g; ++j) rep += sr.shared_tail[j];
     if (empty_tail > 0) {
         // the segment's last slots hold rows without a record that no record references: the
         // launches end before them. A STORE leaves them unwritten (nothing gathers them); their
@@ -1615,9 +1685,8 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
     // 11.26-11.47 ms after, 11.07-11.17 ms beside). Under a restricted capture or
     // without aux streams it follows the layer on the main stream.
     hipStream_t side = nullptr;
-    if (has_shared && hi > lo && L.view && L.view->n_aux > 0 &&
-        !capture_restricted(L.main)) {
-        side = L.view->aux[L.view->n_aux > 1 ? 1 : 0];
+    if (has_shared && hi > lo && L.ss && L.ss->n_aux > 0 && !capture_restricted(L.main)) {
+        side = L.ss->aux[L.ss->n_aux > 1 ? 1 : 0];
         if (int e = link(sc, L.main, side)) return e;
         if (int e = wait_late(side, dp)) return e;
         if (int e = shared_mean(side)) return e;
@@ -1631,25 +1700,22 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
         return shared_mean(L.main);
     }
     const int h = (k - 1) * kSegs + g;
-    lgcn_sched v;
-    const lgcn_sched* vp = nullptr;
-    if (L.view) {
-        v = *L.view;
-        v.t0 = sc->timing_sides ? sc->timing_sides[2 * h] : nullptr;
-        v.t1 = sc->timing_sides ? sc->timing_sides[2 * h + 1] : nullptr;
-        v.trace = sc->trace_sides ? sc->trace_sides + h * 8 : nullptr;
-        vp = &v;
+    Marks mk{};
+    if (L.ss) {
+        mk.t0 = sc->timing_sides ? sc->timing_sides[2 * h] : nullptr;
+        mk.t1 = sc->timing_sides ? sc->timing_sides[2 * h + 1] : nullptr;
+        mk.trace = sc->trace_sides ? sc->trace_sides + h * 8 : nullptr;
     }
     Deps local;
     Deps* dq = dp;
-    if (!vp && dp && dp->defer && sc) {
-        // (no view: everything runs on L.main; plan_layer records nothing without a schedule)
+    if (!L.ss && dp && dp->defer && sc) {
+        // (no stream set: everything runs on L.main; plan_layer records nothing without one)
         local = *dp;
         local.defer = false;
         dq = &local;
     }
     if (int e = plan_layer(rowptr + lo, edges, row_ids + lo, hi - lo, plans[2 * g + (k & 1)],
-                           io.x, io.xdiv, io.x_nz, io.y, d, d, io.ep, vp, L.main, dq))
+                           io.x, io.xdiv, io.x_nz, io.y, d, d, io.ep, sc, L.ss, mk, L.main, dq))
         return e;
     if (dq == &local)
         for (int i = 0; i < 2; ++i)
@@ -1672,16 +1738,12 @@ int seg_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
 // Backward buffers alternate (layer k overwrites layer k-2's rows): a part of side 1 overwrites
 // rows that only the classes it waited for read, and a class of side 0 overwrites rows that only
 // the parts it waited for read.
-int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* row_ids,
-              const lgcn_sides_t& sd, const lgcn_hub_plan_t* plans, int32_t d, int32_t K,
-              const std::function<LayerIO(int)>& layer, const lgcn_sched* sched, hipStream_t s,
-              const int32_t* empty_tail = nullptr, const lgcn_shared_t* sh = nullptr) {
-    // shared rows (lgcn_shared_t): side 1 reads the re-pointed records from layer 2 on; `edges`
-    // and `row_ids` are the caller's edges_l1 and partitioned row ids
-    const lgcn_edge_t* edges_ln = sh ? sh->edges_ln : edges;
-    int32_t rep_off[kSegs] = {0, 0, 0, 0};
-    if (sh)
-        for (int g = 1; g < kSegs; ++g) rep_off[g] = rep_off[g - 1] + sh->shared_tail[g - 1];
+// sr: the row ids, the records (edges_l1: what side 0 reads in every layer and side 1 in layer 1;
+// edges_ln: side 1 from layer 2 on) and the tails of the segments (lgcn_shared_t; a propagation
+// without lean or shared rows: its one edge array twice and no tails).
+int run_sides(const int32_t* rowptr, const lgcn_shared_t& sr, const lgcn_sides_t& sd,
+              const lgcn_hub_plan_t* plans, int32_t d, int32_t K,
+              const std::function<LayerIO(int)>& layer, const lgcn_sched* sched, hipStream_t s) {
     Lane lanes[2];
     bool l1_aux = false;
     if (sched) sched->pool->next = 0;
@@ -1716,15 +1778,15 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
             // side 0's mean layer (lane 0, the critical path) started ~1.3 ms after the walk it
             // waits for; sharing the queues they overlap (round 6: C3 forward -0.25..0.35 ms)
             if (k == K && mean && sched && sched->lk_normal && two && l1_aux && !cap &&
-                sched->n_aux >= 3)
-                dp.lk = sched->aux[2];
+                sched->lane0.n_aux >= 3)
+                dp.lk = sched->lane0.aux[2];
             if (mean && k >= 2) {  // the layer kernel's rows read layer K-1's layer-kernel rows
                 dp.late[0] = rest[k - 1];
                 dp.late_emu[0] = part[k - 1][0];
                 dp.late_emu[1] = part[k - 1][1];
             }
-            if (int e = seg_layer(rowptr, k >= 2 ? edges_ln : edges, row_ids, sd.split, n, plans,
-                                  k, 3, io, d, sched, L, &dp, empty_tail ? empty_tail[3] : 0))
+            if (int e = seg_layer(rowptr, k >= 2 ? sr.edges_ln : sr.edges_l1, sr, sd.split, n,
+                                  plans, k, 3, io, d, sched, L, &dp))
                 return e;
             if (k < K && sched) {
                 if (int e = record(sched, L.main, &rest[k])) return e;
@@ -1745,10 +1807,8 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
                     if (int e = wait_ev(L.main, part[k - 1][0])) return e;
                 Deps dp;
                 if (mean && k >= 2) dp.late[0] = cls[k - 1][c];
-                if (int e = seg_layer(rowptr, edges, row_ids, lo[c], seg_hi(c, n), plans, k, c,
-                                      io, d, sched, L, &dp, empty_tail ? empty_tail[c] : 0,
-                                      sh ? sh->shared_tail[c] : 0,
-                                      sh ? sh->rep + rep_off[c] : nullptr))
+                if (int e = seg_layer(rowptr, sr.edges_l1, sr, lo[c], seg_hi(c, n), plans, k, c,
+                                      io, d, sched, L, &dp))
                     return e;
                 if (sched)
                     if (int e = record(sched, L.main, &cls[k][c])) return e;
@@ -1757,6 +1817,49 @@ int run_sides(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* ro
         }
     }
     return join_lanes(sched, two, lanes[1], s);
+}
+// Row ids and records of a sided propagation without shared rows (lgcn_shared_t): one edge array
+// for every layer; empty_tail: NULL (none) or the segments' empty tails.
+lgcn_shared_t plain_rows(const int32_t* row_ids, const lgcn_edge_t* edges,
+                         const int32_t* empty_tail) {
+    lgcn_shared_t sr;
+    memset(&sr, 0, sizeof(sr));
+    sr.row_ids = row_ids;
+    sr.edges_l1 = sr.edges_ln = edges;
+    if (empty_tail) memcpy(sr.empty_tail, empty_tail, sizeof(sr.empty_tail));
+    return sr;
+}
+
+// The sided forward behind lgcn_propagate_forward_sides, _lean and _shared. ptrs_ok: the entry
+// point's own pointers (checked where `out` is).
+int forward_sides(const int32_t* rowptr, const lgcn_sides_t* sides, const lgcn_hub_plan_t* plans,
+                  const lgcn_shared_t& in, bool ptrs_ok, const lgcn_rows_t& emb, int32_t d,
+                  int32_t K, float* const* layer_bufs_host, float* out, const lgcn_sched* sched,
+                  void* stream) {
+    const int32_t n = sides ? sides->n : -1;
+    hipStream_t s = S(stream);
+    int rc;
+    if (prologue(n, d, K, out && ptrs_ok, layer_bufs_host, emb, out, true, s, &rc)) return rc;
+    if (int e = check_sides(rowptr, in.row_ids, n, sides, plans)) return e;
+    // every pair of tails inside its segment; shared rows are side-0 rows and need their arrays
+    const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
+    bool any = false;
+    for (int g = 0; g < kSegs; ++g) {
+        const int32_t et = in.empty_tail[g], st = in.shared_tail[g];
+        if (et < 0 || st < 0 || (int64_t)et + st > b[g + 1] - b[g]) return LGCN_EINVAL;
+        any = any || st > 0;
+    }
+    if (in.shared_tail[3] != 0) return LGCN_EINVAL;
+    // one side-0 segment only: a class's mean waits for its own class's layer K-1 alone, and a
+    // representative in another class would be read without a wait
+    if ((in.shared_tail[0] > 0) + (in.shared_tail[1] > 0) + (in.shared_tail[2] > 0) > 1)
+        return LGCN_EINVAL;
+    if (any && (!in.row_ids || !in.edges_l1 || !in.edges_ln || !in.rep)) return LGCN_EINVAL;
+    // K = 1 has no intermediate layer to share: the lean forward over the partitioned slots
+    const lgcn_shared_t sr =
+        K >= 2 && any ? in : plain_rows(in.row_ids, in.edges_l1, in.empty_tail);
+    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
+    return run_sides(rowptr, sr, *sides, plans, d, K, layer, sched, s);
 }
 }  // namespace
 
@@ -1776,44 +1879,25 @@ int lgcn_sched_create(void* const* aux_streams, int32_t n_aux, lgcn_sched_t** ou
     memset(sc, 0, sizeof(*sc));
     sc->pool = pool;
     const int n0 = n_aux < 3 ? n_aux : 3;
-    sc->n_aux = n0;
+    sc->lane0.n_aux = sc->lane0_rev.n_aux = n0;
     sc->chain = 1;
     sc->classes = 1;
     sc->lk_normal = 1;
-    for (int i = 0; i < n0; ++i) sc->aux[i] = reinterpret_cast<hipStream_t>(aux_streams[i]);
+    for (int i = 0; i < n0; ++i) {
+        sc->lane0.aux[i] = reinterpret_cast<hipStream_t>(aux_streams[i]);
+        sc->lane0_rev.aux[n0 - 1 - i] = sc->lane0.aux[i];
+    }
+    if (n_aux >= 4) {
+        sc->lane1_main = reinterpret_cast<hipStream_t>(aux_streams[3]);
+        sc->lane1.n_aux = n_aux - 4;
+        for (int i = 0; i < n_aux - 4; ++i)
+            sc->lane1.aux[i] = reinterpret_cast<hipStream_t>(aux_streams[4 + i]);
+    }
     int e = 0;
     for (; pool->n < kPoolEvents && !e; ++pool->n)
         e = herr(hipEventCreateWithFlags(&pool->ev[pool->n], hipEventDisableTiming));
-    if (e) --pool->n;  // (the failed slot holds no event)
-    if (!e) {
-        sc->lane1s = new (std::nothrow) lgcn_sched();
-        if (!sc->lane1s) e = LGCN_EINVAL;
-        if (!e) {
-            lgcn_sched* l1 = sc->lane1s;
-            memset(l1, 0, sizeof(*l1));
-            l1->pool = pool;
-            l1->n_aux = n0;
-            l1->chain = 1;
-            l1->classes = 1;
-            for (int i = 0; i < n0; ++i) l1->aux[i] = sc->aux[n0 - 1 - i];
-        }
-    }
-    if (!e && n_aux >= 4) {
-        sc->lane1_main = reinterpret_cast<hipStream_t>(aux_streams[3]);
-        sc->lane1 = new (std::nothrow) lgcn_sched();
-        if (!sc->lane1) e = LGCN_EINVAL;
-        if (!e) {
-            lgcn_sched* l1 = sc->lane1;
-            memset(l1, 0, sizeof(*l1));
-            l1->pool = pool;
-            l1->n_aux = n_aux - 4;
-            l1->chain = 1;
-            l1->classes = 1;
-            for (int i = 0; i < l1->n_aux; ++i)
-                l1->aux[i] = reinterpret_cast<hipStream_t>(aux_streams[4 + i]);
-        }
-    }
     if (e) {
+        --pool->n;  // (the failed slot holds no event)
         lgcn_sched_destroy(sc);
         return e;
     }
@@ -1827,8 +1911,6 @@ int lgcn_sched_destroy(lgcn_sched_t* sc) {
         for (int i = 0; i < sc->pool->n; ++i) (void)hipEventDestroy(sc->pool->ev[i]);
         delete sc->pool;
     }
-    delete sc->lane1;  // (views: share the root's pool)
-    delete sc->lane1s;
     delete sc;
     return 0;
 }
@@ -1840,25 +1922,21 @@ int lgcn_sched_set(lgcn_sched_t* sc, int32_t knob, int64_t value) {
         case LGCN_SCHED_SLOTS1:
             if (value < 0 || value > LGCN_EMU_MAX_WALK_SLOTS) return LGCN_EINVAL;
             sc->slots[knob - LGCN_SCHED_SLOTS0] = (int32_t)value;
-            if (sc->lane1) sc->lane1->slots[knob - LGCN_SCHED_SLOTS0] = (int32_t)value;
-            if (sc->lane1s) sc->lane1s->slots[knob - LGCN_SCHED_SLOTS0] = (int32_t)value;
             return 0;
         case LGCN_SCHED_CHAIN:
             sc->chain = value != 0;
-            if (sc->lane1) sc->lane1->chain = value != 0;
-            if (sc->lane1s) sc->lane1s->chain = value != 0;
             return 0;
         case LGCN_SCHED_LANE1_SHARED:
             sc->lane1_shared = value != 0;
             return 0;
         case LGCN_SCHED_TIMING_START:
-            sc->t0 = reinterpret_cast<hipEvent_t>(value);
+            sc->marks.t0 = reinterpret_cast<hipEvent_t>(value);
             return 0;
         case LGCN_SCHED_TIMING_END:
-            sc->t1 = reinterpret_cast<hipEvent_t>(value);
+            sc->marks.t1 = reinterpret_cast<hipEvent_t>(value);
             return 0;
         case LGCN_SCHED_TRACE:
-            sc->trace = reinterpret_cast<hipEvent_t*>(value);
+            sc->marks.trace = reinterpret_cast<hipEvent_t*>(value);
             return 0;
         case LGCN_SCHED_TRACE_SIDES:
             sc->trace_sides = reinterpret_cast<hipEvent_t*>(value);
@@ -1897,7 +1975,8 @@ int lgcn_layer(const int32_t* rowptr, const lgcn_edge_t* edges, const int32_t* r
     if (epi_host->mode != LGCN_EPI_ADD && (x_div != 1.f || x_nz)) return LGCN_EINVAL;
     if (sched) sched->pool->next = 0;
     return plan_layer(rowptr, edges, row_ids, n_rows, *plan, x, x_div, x_nz, y, ldy, d,
-                      *epi_host, sched, S(stream));
+                      *epi_host, sched, sched ? &sched->lane0 : nullptr,
+                      sched ? sched->marks : Marks{}, S(stream));
 }
 
 int lgcn_propagate_forward(const int32_t* rowptr, const lgcn_edge_t* edges,
@@ -1905,42 +1984,11 @@ int lgcn_propagate_forward(const int32_t* rowptr, const lgcn_edge_t* edges,
                            lgcn_rows_t emb, int32_t d,
                            int32_t K, float* const* layer_bufs_host, float* out,
                            void* const* ev_host, const lgcn_sched_t* sched, void* stream) {
-    if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || !out) return LGCN_EINVAL;
-    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
-    if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
     hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
-    if (int e = check_plan(plan)) return e;
-    if (sched) sched->pool->next = 0;
-    for (int k = 1; k <= K; ++k) {
-        const lgcn_rows_t x = (k == 1) ? emb : dense_rows(layer_bufs_host[k - 2], n, d);
-        lgcn_epilogue_t ep;
-        memset(&ep, 0, sizeof(ep));
-        float* y;
-        if (k < K) {
-            ep.mode = LGCN_EPI_STORE;
-            y = layer_bufs_host[k - 1];
-        } else {
-            ep.mode = LGCN_EPI_MEAN;
-            ep.n_prev = K;
-            ep.div = (float)(K + 1);
-            ep.prev0 = emb;
-            for (int i = 0; i + 1 < K; ++i) ep.prev_dense[i] = layer_bufs_host[i];
-            ep.ld_prev = d;
-            y = out;
-        }
-        if (ev_host) {
-            if (int e = herr(hipEventRecord((hipEvent_t)ev_host[2 * (k - 1)], s))) return e;
-        }
-        if (int e = plan_layer(rowptr, edges, row_ids, n, *plan, x, 1.f, nullptr, y, d, d, ep,
-                               sched, s))
-            return e;
-        if (ev_host) {
-            if (int e = herr(hipEventRecord((hipEvent_t)ev_host[2 * (k - 1) + 1], s))) return e;
-        }
-    }
-    return 0;
+    int rc;
+    if (prologue(n, d, K, out != nullptr, layer_bufs_host, emb, out, true, s, &rc)) return rc;
+    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
+    return run_layers(rowptr, edges, row_ids, n, plan, d, K, layer, ev_host, sched, s);
 }
 
 int lgcn_propagate_forward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,
@@ -1948,8 +1996,8 @@ int lgcn_propagate_forward_sides(const int32_t* rowptr, const lgcn_edge_t* edges
                                  const lgcn_hub_plan_t* plans, lgcn_rows_t emb, int32_t d,
                                  int32_t K, float* const* layer_bufs_host, float* out,
                                  const lgcn_sched_t* sched, void* stream) {
-    return lgcn_propagate_forward_sides_lean(rowptr, edges, row_ids, sides, plans, nullptr, emb, d,
-                                             K, layer_bufs_host, out, sched, stream);
+    return forward_sides(rowptr, sides, plans, plain_rows(row_ids, edges, nullptr), true, emb, d,
+                         K, layer_bufs_host, out, sched, stream);
 }
 
 int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* edges,
@@ -1958,23 +2006,9 @@ int lgcn_propagate_forward_sides_lean(const int32_t* rowptr, const lgcn_edge_t* 
                                       lgcn_rows_t emb, int32_t d, int32_t K,
                                       float* const* layer_bufs_host, float* out,
                                       const lgcn_sched_t* sched, void* stream) {
-    const int32_t n = sides ? sides->n : -1;
-    if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || !out) return LGCN_EINVAL;
-    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
-    if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
-    hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
-    if (int e = check_sides(rowptr, row_ids, n, sides, plans)) return e;
-    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
-    if (lean) {  // every tail inside its segment
-        const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
-        for (int g = 0; g < kSegs; ++g)
-            if (lean->empty_tail[g] < 0 || lean->empty_tail[g] > b[g + 1] - b[g])
-                return LGCN_EINVAL;
-    }
-    return run_sides(rowptr, edges, row_ids, *sides, plans, d, K, layer, sched, s,
-                     lean ? lean->empty_tail : nullptr);
+    return forward_sides(rowptr, sides, plans,
+                         plain_rows(row_ids, edges, lean ? lean->empty_tail : nullptr), true, emb,
+                         d, K, layer_bufs_host, out, sched, stream);
 }
 
 int lgcn_propagate_forward_sides_shared(const int32_t* rowptr, const lgcn_sides_t* sides,
@@ -1982,32 +2016,8 @@ int lgcn_propagate_forward_sides_shared(const int32_t* rowptr, const lgcn_sides_
                                         lgcn_rows_t emb, int32_t d, int32_t K,
                                         float* const* layer_bufs_host, float* out,
                                         const lgcn_sched_t* sched, void* stream) {
-    const int32_t n = sides ? sides->n : -1;
-    if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || !out || !sh) return LGCN_EINVAL;
-    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // 18 stacked layers: not ATen's order
-    if (K > 1 && !layer_bufs_host) return LGCN_EINVAL;
-    hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(emb, n, d, 1.0f, out, d, s, true);  // mean(stack([E0]))
-    if (int e = check_sides(rowptr, sh->row_ids, n, sides, plans)) return e;
-    // every pair of tails inside its segment; shared rows are side-0 rows and need their arrays
-    const int32_t b[kSegs + 1] = {0, sides->class_end[0], sides->class_end[1], sides->split, n};
-    bool any = false;
-    for (int g = 0; g < kSegs; ++g) {
-        const int32_t et = sh->empty_tail[g], st = sh->shared_tail[g];
-        if (et < 0 || st < 0 || (int64_t)et + st > b[g + 1] - b[g]) return LGCN_EINVAL;
-        any = any || st > 0;
-    }
-    if (sh->shared_tail[3] != 0) return LGCN_EINVAL;
-    // one side-0 segment only: a class's mean waits for its own class's layer K-1 alone, and a
-    // representative in another class would be read without a wait
-    if ((sh->shared_tail[0] > 0) + (sh->shared_tail[1] > 0) + (sh->shared_tail[2] > 0) > 1)
-        return LGCN_EINVAL;
-    if (any && (!sh->row_ids || !sh->edges_l1 || !sh->edges_ln || !sh->rep)) return LGCN_EINVAL;
-    auto layer = [&](int k) { return forward_io(k, K, emb, layer_bufs_host, out, n, d); };
-    // K = 1 has no intermediate layer to share: the lean forward over the partitioned slots
-    return run_sides(rowptr, sh->edges_l1, sh->row_ids, *sides, plans, d, K, layer, sched, s,
-                     sh->empty_tail, K >= 2 && any ? sh : nullptr);
+    return forward_sides(rowptr, sides, plans, sh ? *sh : plain_rows(nullptr, nullptr, nullptr),
+                         sh != nullptr, emb, d, K, layer_bufs_host, out, sched, stream);
 }
 
 int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edges,
@@ -2016,31 +2026,18 @@ int lgcn_propagate_backward_sides(const int32_t* rowptr, const lgcn_edge_t* edge
                                   const uint32_t* grad_nz, int32_t d, int32_t K, float* work_h,
                                   float* grad_e0, const lgcn_sched_t* sched, void* stream) {
     const int32_t n = sides ? sides->n : -1;
-    if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || !grad_out.p0 || !grad_e0) return LGCN_EINVAL;
-    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // the backward of a forward that is refused
     hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(grad_out, n, d, 1.0f, grad_e0, d, s);
-    if (K > 1 && !work_h) return LGCN_EINVAL;
+    int rc;
+    if (prologue(n, d, K, grad_out.p0 && grad_e0, work_h, grad_out, grad_e0, false, s, &rc))
+        return rc;
     if (int e = check_sides(rowptr, row_ids, n, sides, plans)) return e;
-    // as lgcn_propagate_backward: h = G/(K+1) + Âᵀ h, layer k into grad_e0 or work_h alternately
-    auto out_of = [&](int k) { return ((K - k) % 2 == 0) ? grad_e0 : work_h; };
     auto layer = [&](int k) {
-        LayerIO io;
-        memset(&io, 0, sizeof(io));
-        io.x = k == 1 ? grad_out : dense_rows(out_of(k - 1), n, d);
-        io.xdiv = k == 1 ? (float)(K + 1) : 1.f;
-        io.x_nz = k == 1 ? grad_nz : nullptr;
-        io.y = out_of(k);
-        io.ep.mode = LGCN_EPI_ADD;
-        io.ep.addend = grad_out;
-        io.ep.addend_nz = grad_nz;
-        io.ep.div = (float)(K + 1);
-        return io;
+        return backward_io(k, K, grad_out, grad_nz, work_h, grad_e0, n, d);
     };
     // (round 5: the backward with its lanes flipped, the high-priority lane carrying the chain
     // of half-layers that starts with side 0, measured 9.74 / 9.76 vs 9.65 / 9.64 ms: not kept)
-    return run_sides(rowptr, edges, row_ids, *sides, plans, d, K, layer, sched, s);
+    return run_sides(rowptr, plain_rows(row_ids, edges, nullptr), *sides, plans, d, K, layer,
+                     sched, s);
 }
 
 int lgcn_propagate_backward(const int32_t* rowptr, const lgcn_edge_t* edges,
@@ -2048,36 +2045,14 @@ int lgcn_propagate_backward(const int32_t* rowptr, const lgcn_edge_t* edges,
                             lgcn_rows_t grad_out,
                             const uint32_t* grad_nz, int32_t d, int32_t K, float* work_h,
                             float* grad_e0, const lgcn_sched_t* sched, void* stream) {
-    if (int e = valid_geom(n, d)) return e;
-    if (K < 0 || !grad_out.p0 || !grad_e0) return LGCN_EINVAL;
-    if (K > LGCN_MAX_LAYERS) return LGCN_ETOOMANY;  // the backward of a forward that is refused
     hipStream_t s = S(stream);
-    if (K == 0) return scale_rows(grad_out, n, d, 1.0f, grad_e0, d, s);
-    if (K > 1 && !work_h) return LGCN_EINVAL;
-    if (int e = check_plan(plan)) return e;
-    if (sched) sched->pool->next = 0;
-    // MeanBackward hands every layer c = G / (K+1); it is never materialised: layer 1 gathers
-    // G / (K+1) on load and every epilogue adds G[row] / (K+1) (same rounding as c).
-    const float div = (float)(K + 1);
-    lgcn_epilogue_t ep;
-    memset(&ep, 0, sizeof(ep));
-    ep.mode = LGCN_EPI_ADD;
-    ep.addend = grad_out;
-    ep.addend_nz = grad_nz;
-    ep.div = div;
-    lgcn_rows_t h = grad_out;
-    float xdiv = div;
-    const uint32_t* x_nz = grad_nz;
-    for (int k = 1; k <= K; ++k) {
-        float* y = ((K - k) % 2 == 0) ? grad_e0 : work_h;
-        if (int e = plan_layer(rowptr, edges, row_ids, n, *plan, h, xdiv, x_nz, y, d, d, ep, sched,
-                               s))
-            return e;
-        h = dense_rows(y, n, d);
-        xdiv = 1.f;
-        x_nz = nullptr;
-    }
-    return 0;
+    int rc;
+    if (prologue(n, d, K, grad_out.p0 && grad_e0, work_h, grad_out, grad_e0, false, s, &rc))
+        return rc;
+    auto layer = [&](int k) {
+        return backward_io(k, K, grad_out, grad_nz, work_h, grad_e0, n, d);
+    };
+    return run_layers(rowptr, edges, row_ids, n, plan, d, K, layer, nullptr, sched, s);
 }
 
 }  // extern "C"

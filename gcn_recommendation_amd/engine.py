@@ -898,12 +898,18 @@ class SharedPlan:
         return torch.cat([self.row_ids_s[a:b] for a, b in self.tail_slots]).long()
 
     def struct(self):
-        st = SharedT()
-        for g in range(N_SEGS):
-            st.empty_tail[g], st.shared_tail[g] = self.empty_tail[g], self.shared_tail[g]
-        st.row_ids, st.edges_l1 = self.row_ids_s.data_ptr(), self.edges_l1.data_ptr()
-        st.edges_ln, st.rep = self.edges_ln.data_ptr(), self.rep.data_ptr()
-        return st
+        return _shared_struct(self.row_ids_s, self.edges_l1, self.edges_ln, self.rep,
+                              self.empty_tail, self.shared_tail)
+
+
+def _shared_struct(row_ids, edges_l1, edges_ln, rep=None, empty_tail=(0,) * N_SEGS,
+                   shared_tail=(0,) * N_SEGS):
+    """lgcn_shared_t; without shared rows: the graph's own row ids, its edges twice, no rep."""
+    st = SharedT()
+    st.empty_tail[:], st.shared_tail[:] = empty_tail, shared_tail
+    st.row_ids, st.edges_l1, st.edges_ln, st.rep = (
+        None if t is None else t.data_ptr() for t in (row_ids, edges_l1, edges_ln, rep))
+    return st
 
 
 def shared_plan(rowptr, edges, row_ids, split, segments, lean):
@@ -1408,6 +1414,11 @@ def _aligned16(segments):
                for t in segments)
 
 
+def _chains(d, aligned):
+    """The chain kernel takes the plans' chain rows: it is on, takes d, and X is 16-B aligned."""
+    return chain_enabled() and bool(load_library().lgcn_chain_supported(d)) and aligned
+
+
 def emu_slots():
     """LDS slots of the walk (part 0, part 1): 20, 8 — the longest rows run few waves and take
     many slots; part 1's rows are more waves, and fewer slots fit more of them per CU (C3
@@ -1440,7 +1451,7 @@ def spmm_layer(graph, x_segments, y, d, epi, hub_threshold, hubs=None, stream=No
     main = torch.cuda.current_stream(graph.device)
     if main.cuda_stream != (stream.value or 0):
         raise LgcnError("spmm_layer: stream must be the device's current stream")
-    chains = chain_enabled() and bool(lib.lgcn_chain_supported(d)) and _aligned16(x_segments)
+    chains = _chains(d, _aligned16(x_segments))
     plan = hp.struct(d, graph.device, nnz=graph.nnz, walk_all=not chains,
                      live=x_nz is not None and live_enabled(), backward=backward)
     x = rows_desc(x_segments, d)
@@ -1488,9 +1499,8 @@ def _side_plans(graph, d, hub_threshold, hub_mode, emu_min, xs_aligned, live=Fal
     """The 8 lgcn_hub_plan_t of lgcn_propagate_*_sides: plans[2 * segment + set] (segments: the
     side-0 classes, side 1). live: attach the live-edge scratch (the backward of a row-sparse
     G). part0: the part-0 cut in blocks (walk_cut_blocks)."""
-    lib = load_library()
     hps = graph.side_hubs(hub_threshold, mode=hub_mode, emu_min=emu_min)
-    chains = chain_enabled() and bool(lib.lgcn_chain_supported(d)) and xs_aligned
+    chains = _chains(d, xs_aligned)
     arr = (PlanT * (2 * N_SEGS))()
     for g in range(N_SEGS):
         for j in (0, 1):
@@ -1572,6 +1582,18 @@ def _collect_sides(ev, K, graph):
                            for k in range(1, K + 1) for g in segs})
 
 
+def _run_sided(what, call, sc, K, graph):
+    """One call of the sided entry point `what`, call(sched handle), under the schedule sc: its
+    side_timing / side_trace events set for the call and cleared after it, last_schedule."""
+    ev = _SideEvents(sc, K, side_timing is not None, side_trace is not None)
+    try:
+        _check(call(sc.handle if sc is not None else None), what)
+    finally:
+        ev.clear()
+    _note_schedule(sc, graph)
+    _collect_sides(ev, K, graph)
+
+
 def _check_depth(K):
     """K = 0..LGCN_MAX_LAYERS: torch.mean over 18 stacked layers (K = 17) no longer sums them
     one after the other, so the forward and its backward stop at 16."""
@@ -1593,8 +1615,8 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
     layer_events: optional list of (start, end) torch.cuda.Event pairs recorded on the current
     stream around each whole layer (every stream of it joined); kernel_events: the same around
     each layer's layer-kernel launch alone (spmm_layer) — bench.py's live timing. A side-ordered
-    graph runs the bipartite two-lane schedule (lgcn_propagate_forward_sides) unless per-layer
-    events are asked for.
+    graph runs the bipartite two-lane schedule (lgcn_propagate_forward_sides_shared) unless
+    per-layer events are asked for.
     lean: the sided forward without the rows its result does not need (LeanPlan: the layer
     buffers' `empty` rows stay unwritten; same final bits, exact and chunk plans alike). None:
     on when the layers are private to the call (no return_layers); True with return_layers hands
@@ -1634,36 +1656,24 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
                 lean = share or not return_layers
             if share and not lean:
                 raise LgcnError("share=True needs lean: the shared rows sit before the empty tail")
-            lp = graph.lean().struct() if lean else None
             # (K = 1 has no intermediate layer; rows of one record are bundle rows from a hub
             # threshold of 1 on)
-            sp = graph.shared() if share and K >= 2 and hub_threshold >= 1 else None
-            if sp is not None and sp.n_shared == 0:
-                sp = None
+            if share and K >= 2 and hub_threshold >= 1 and graph.shared().n_shared:
+                st = graph.shared().struct()
+            elif lean:  # the lean tails, else none, over the graph's own arrays
+                st = _shared_struct(graph.row_ids, graph.edges, graph.edges,
+                                    empty_tail=graph.lean().empty_tail)
+            else:
+                st = _shared_struct(graph.row_ids, graph.edges, graph.edges)
             plans, _ = _side_plans(graph, d, hub_threshold, hub_mode, emu_min,
                                    _aligned16(segments))
-            sc = sched_for(dev)
-            ev = _SideEvents(sc, K, side_timing is not None, side_trace is not None)
             bufs = (ctypes.c_void_p * max(K - 1, 1))(*[t.data_ptr() for t in layers])
             sides = graph.sides_struct()
-            try:
-                if sp is not None:
-                    st = sp.struct()
-                    _check(lib.lgcn_propagate_forward_sides_shared(
-                        _ptr(graph.rowptr), ctypes.byref(sides), plans, ctypes.byref(st), e0, d, K,
-                        bufs, _ptr(out), sc.handle if sc is not None else None, stream),
-                        "lgcn_propagate_forward_sides_shared")
-                else:
-                    _check(lib.lgcn_propagate_forward_sides_lean(
-                        _ptr(graph.rowptr), _ptr(graph.edges), _ptr(graph.row_ids),
-                        ctypes.byref(sides), plans, ctypes.byref(lp) if lp is not None else None,
-                        e0, d, K, bufs, _ptr(out),
-                        sc.handle if sc is not None else None, stream),
-                        "lgcn_propagate_forward_sides_lean")
-            finally:
-                ev.clear()
-            _note_schedule(sc, graph)
-            _collect_sides(ev, K, graph)
+            _run_sided("lgcn_propagate_forward_sides_shared",
+                       lambda sched: lib.lgcn_propagate_forward_sides_shared(
+                           _ptr(graph.rowptr), ctypes.byref(sides), plans, ctypes.byref(st), e0,
+                           d, K, bufs, _ptr(out), sched, stream),
+                       sched_for(dev), K, graph)
             return (out, layers) if return_layers else out
         hp = graph.hubs(hub_threshold, mode=hub_mode, emu_min=emu_min)
         for k in range(1, K + 1):
@@ -1683,15 +1693,15 @@ def propagate_forward(graph, segments, K, hub_threshold=None, layer_events=None,
         return (out, layers) if return_layers else out
 
 
-def rows_nonzero(segments, d, device):
+def rows_nonzero(segments, d, device, ld=None):
     """(bitmask of rows holding a nonzero, device int32 count of such rows): lgcn_rows_nonzero.
-    Nothing is read back."""
+    Nothing is read back. ld: the segments' row stride (default d)."""
     lib = load_library()
     n = sum(int(t.shape[0]) for t in segments)
     mask = torch.empty(max((n + 31) // 32, 1), dtype=torch.int32, device=device)
     count = torch.empty(1, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _check(lib.lgcn_rows_nonzero(rows_desc(segments, d), n, d, _ptr(mask), _ptr(count),
+        _check(lib.lgcn_rows_nonzero(rows_desc(segments, ld or d), n, d, _ptr(mask), _ptr(count),
                                      _stream(device)), "lgcn_rows_nonzero")
     return mask, count
 
@@ -1770,14 +1780,7 @@ def _sampled_live_count(segs, d, dev):
     views = [t[::S] for t in segs if t.shape[0] > 0]
     if not views:
         return None
-    lib = load_library()
-    n = sum(int(v.shape[0]) for v in views)
-    mask = torch.empty(max((n + 31) // 32, 1), dtype=torch.int32, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.lgcn_rows_nonzero(rows_desc(views, S * d), n, d, _ptr(mask), _ptr(count),
-                                     _stream(dev)), "lgcn_rows_nonzero")
-    return count
+    return rows_nonzero(views, d, dev, ld=S * d)[1]
 
 
 def _backward_role(dev, n, cnt, scale=1):
@@ -1851,19 +1854,12 @@ def propagate_backward(graph, grad_out, K, hub_threshold=None, sparse=None, hub_
                                    live=nz is not None, backward=True,
                                    part0=PART0_SPARSE_BACKWARD
                                    if role == "backward" and not any(gt.class_parts) else None)
-            sc = sched_for(dev, role=role)
-            ev = _SideEvents(sc, K, side_timing is not None, side_trace is not None)
             sides = gt.sides_struct()
-            try:
-                _check(lib.lgcn_propagate_backward_sides(
-                    _ptr(gt.rowptr), _ptr(gt.edges), _ptr(gt.row_ids), ctypes.byref(sides),
-                    plans, g, _ptr(nz), d, K, _ptr(work), _ptr(out),
-                    sc.handle if sc is not None else None, stream),
-                    "lgcn_propagate_backward_sides")
-            finally:
-                ev.clear()
-            _note_schedule(sc, gt)
-            _collect_sides(ev, K, gt)
+            _run_sided("lgcn_propagate_backward_sides",
+                       lambda sched: lib.lgcn_propagate_backward_sides(
+                           _ptr(gt.rowptr), _ptr(gt.edges), _ptr(gt.row_ids), ctypes.byref(sides),
+                           plans, g, _ptr(nz), d, K, _ptr(work), _ptr(out), sched, stream),
+                       sched_for(dev, role=role), K, gt)
             return out
         if cnt is not None and not torch.cuda.is_current_stream_capturing():
             _hint_push(dev, cnt, scale)

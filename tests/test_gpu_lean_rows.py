@@ -12,6 +12,8 @@ Each case (d, K, kind of E0): the lean forward is bitwise the forward with lean=
 C oracle wherever that is not NaN (NaN positions equal), and the graph's derived / empty counts
 equal a numpy count (nonzero, so the test cannot pass with nothing left out). One test fills the
 layer buffers with NaN and checks that the skipped rows are neither written nor read."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -167,3 +169,40 @@ def test_skipped_rows_are_not_written(gpu_device, monkeypatch, K):
     for k, lay in enumerate(layers):
         assert torch.isnan(lay[skipped]).all(), k         # left as allocated
         assert not torch.isnan(lay[~skipped]).any(), k    # every other row produced
+
+
+def test_lean_entry_point_called_directly(gpu_device, monkeypatch):
+    """lgcn_propagate_forward_sides_lean itself (propagate_forward reaches the sided forward
+    through the _shared entry point): `out` is bitwise the Python lean forward and the rows
+    without a record stay unwritten; with lean = NULL the same bits and every row written."""
+    g = _graph(gpu_device, monkeypatch)
+    z = _case()
+    d, K, n = 64, 3, z["n"]
+    x = _segs(_e0(z, d, "random"), z["U"], gpu_device)
+    want = engine.propagate_forward(g, x, K, lean=True, share=False, **KW)
+    lib = engine.load_library()
+    plans, hps = engine._side_plans(g, d, KW["hub_threshold"], KW["hub_mode"], KW["emu_min"],
+                                    engine._aligned16(x))
+    sc = engine.sched_for(gpu_device)
+    sides = g.sides_struct()
+    skipped = torch.from_numpy(z["deg"] == 0).to(gpu_device)
+    P = engine._ptr
+    for lean in (g.lean().struct(), None):
+        layers = [torch.full((n, d), float("nan"), dtype=torch.float32, device=gpu_device)
+                  for _ in range(K - 1)]
+        bufs = (ctypes.c_void_p * (K - 1))(*[t.data_ptr() for t in layers])
+        out = torch.empty((n, d), dtype=torch.float32, device=gpu_device)
+        with torch.cuda.device(gpu_device):
+            rc = lib.lgcn_propagate_forward_sides_lean(
+                P(g.rowptr), P(g.edges), P(g.row_ids), ctypes.byref(sides), plans,
+                None if lean is None else ctypes.byref(lean), engine.rows_desc(x, d), d, K, bufs,
+                P(out), None if sc is None else sc.handle, engine._stream(gpu_device))
+        assert rc == 0
+        assert torch.equal(out.view(torch.int32), want.view(torch.int32))
+        for k, lay in enumerate(layers):
+            if lean is not None:
+                assert torch.isnan(lay[skipped]).all(), k
+                assert not torch.isnan(lay[~skipped]).any(), k
+            else:
+                assert not torch.isnan(lay).any(), k
+    del hps  # (the plans' scratch lives until here)

@@ -3,6 +3,8 @@
 Bar: bitwise wherever the engine runs the reference's sequential order (every row with degree
 <= hub threshold; all rows under LGCN_HUB_THRESHOLD=exact); otherwise, for chunked hub rows,
 the north_star tolerance max|got-ref| <= 1e-5 * max|ref| per tensor."""
+import warnings
+
 import numpy as np
 import pytest
 import torch
@@ -234,7 +236,8 @@ def test_c_abi_whole_forward_backward(gpu_device, monkeypatch, order, mode):
     """lgcn_propagate_forward / lgcn_propagate_backward — the one-call entry points a C host
     binds — equal the per-layer path the Python binding drives, bitwise,
     under each hub plan: chunked hub rows with two-level combines (pre_group 2), the exact plan
-    (whole long rows + emulated rows: bitwise = oracle) and no hub plan at all (chain)."""
+    (whole long rows + emulated rows: bitwise = oracle) and no hub plan at all (chain). One
+    forward pass hands in ev_host: same result, and the events lie in layer order."""
     import ctypes
     monkeypatch.setattr(engine, "DEFAULT_HUB_PRE_GROUP", 2)
     monkeypatch.setattr(engine, "DEFAULT_HUB_CHUNK", 8)   # hub_d32's rows reach degree 60
@@ -270,6 +273,30 @@ def test_c_abi_whole_forward_backward(gpu_device, monkeypatch, order, mode):
                                         ctypes.cast(bufs, ctypes.c_void_p), P(out), None, sc, st)
         assert rc == 0
         assert torch.equal(out, want)
+    # once more with ev_host: 2 K timing events recorded around the layers, in order on one
+    # stream. `first` and the events are materialised (recorded once) before the marker.
+    first, marker = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * K)]
+    out.fill_(float("nan"))
+    for ev in [first] + evs + [marker]:
+        ev.record()
+    ev_host = (ctypes.c_void_p * (2 * K))(*[ev.cuda_event for ev in evs])
+    rc = lib.lgcn_propagate_forward(P(g.rowptr), P(g.edges), P(g.row_ids), n,
+                                    ctypes.byref(plan), engine.rows_desc(segs, d), d, K,
+                                    ctypes.cast(bufs, ctypes.c_void_p), P(out),
+                                    ctypes.cast(ev_host, ctypes.c_void_p), None, st)
+    assert rc == 0
+    assert torch.equal(out, want)
+    torch.cuda.synchronize(gpu_device)
+    reversed_ms = marker.elapsed_time(first)
+    print(f"ev_host: reversed pair {reversed_ms} ms")
+    if reversed_ms < 0:  # (a runtime that clamps a reversed pair could not show a wrong order)
+        times = [marker.elapsed_time(ev) for ev in evs]  # ms after the marker
+        print(f"ev_host: layer starts / ends {times} ms after the marker")
+        for a, b in zip([0.0] + times, times):  # marker <= start_1 <= end_1 <= start_2 <= ...
+            assert a <= b, times
+    else:
+        warnings.warn(f"ev_host order not checked: a reversed event pair reads {reversed_ms} ms")
     ref = oracle.forward(z["adj_row"], z["adj_col"], z["adj_val"], case_e0(z), K)
     if mode != "chunk":
         assert np.array_equal(out.cpu().numpy(), ref)
