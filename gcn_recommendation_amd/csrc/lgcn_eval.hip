@@ -893,3 +893,327 @@ int lgcn_score_rank_lists(const float* user_emb, int64_t ld_u, const int32_t* us
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// lgcn_score_topk_wide: lgcn_score_topk's lists for k up to LGCN_TOPK_WIDE_MAX_K. The tile loop
+// and the candidate filter are k_score_topk's; what differs is where a user's candidates live:
+//  * LDS holds a user's count and threshold only. The candidates go to a per-(split, slot) buffer
+//    in scratch of capacity cap = 2 kp, kp the power of two >= max(k, 32). One tile adds at most
+//    32 entries per user, and a user whose count passes cap - 32 is selected right after the
+//    tile: a buffer cannot overflow (and every position is still checked against cap).
+//  * wide_select (out of line: the tile loop keeps k_score_topk's registers): the user's wave
+//    reads the buffer into its LDS area (cap pairs, at most 2048 = 16 KB), sorts it with a bitonic
+//    network under better(), writes the first k back and sets the threshold. All (score, index)
+//    pairs are distinct, so the sorted order does not depend on the order they arrived in.
+//  * at the end of a split the buffer's first cnt entries are the split's sorted list.
+//  * k_topk_wide_merge: one block per slot. The splits' lists are sorted and disjoint, so the
+//    global rank of an entry is its place in its own list plus its binary-search place in every
+//    other list; an entry with rank < k is stored at [rank]. Only entries >= the largest k-th
+//    score of a full list can have such a rank. No sort, no atomics on the outputs.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kWideMaxK = LGCN_TOPK_WIDE_MAX_K;
+constexpr int kWideMergeThreads = 256;
+constexpr int64_t kWideMergeEntries = 16384;  // lgcn_topk_wide_splits keeps n_splits * k below it
+
+constexpr int wide_kp(int k) {  // the power of two >= max(k, 32)
+    int p = 32;
+    while (p < k) p <<= 1;
+    return p;
+}
+static_assert(wide_kp(kWideMaxK) == 1024, "a wave's sort area is 2 kp <= 2048 pairs");
+
+struct WideState {
+    int32_t cnt[kUsersPerWave];
+    float thr[kUsersPerWave];
+    int32_t mlo[kUsersPerWave];  // as WaveState's
+    int32_t mhi[kUsersPerWave];
+};
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(kLgkm0);
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Sort user u's buffer (cs, ci)[0, cnt) under better(), keep the first K there, set the count and
+// the threshold. ss / si: this wave's LDS area of cap pairs.
+__device__ __noinline__ void wide_select(WideState& st, float* ss, int32_t* si, float* cs,
+                                         int32_t* ci, int u, int K, int cap, int lane) {
+    const int n = min(st.cnt[u], cap);
+    int m = 32;
+    while (m < n) m <<= 1;  // <= cap: cap is a power of two >= 64
+    // the candidates' stores (other lanes' too) have landed before they are read back
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (int e = lane; e < m; e += 64) {  // padding sorts after every candidate
+        ss[e] = e < n ? cs[e] : -INFINITY;
+        si[e] = e < n ? ci[e] : INT32_MAX;
+    }
+    wave_sync();
+    for (int size = 2; size <= m; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = lane; t < (m >> 1); t += 64) {
+                const int i = 2 * t - (t & (stride - 1));
+                const int j = i + stride;
+                const float s1 = ss[i], s2 = ss[j];
+                const int32_t i1 = si[i], i2 = si[j];
+                const bool first = (i & size) == 0;  // this run is sorted best first
+                if (first ? better(s2, i2, s1, i1) : better(s1, i1, s2, i2)) {
+                    ss[i] = s2; si[i] = i2;
+                    ss[j] = s1; si[j] = i1;
+                }
+            }
+            wave_sync();
+        }
+    }
+    const int keep = n < K ? n : K;
+    for (int e = lane; e < keep; e += 64) {
+        cs[e] = ss[e];
+        ci[e] = si[e];
+    }
+    if (lane == 0) {
+        st.cnt[u] = keep;
+        // (no threshold while the K-th best is below -1e10: see compact_user)
+        const float kth = keep == K ? ss[K - 1] : -INFINITY;
+        st.thr[u] = kth < kMasked ? -INFINITY : kth;
+    }
+    wave_sync();
+}
+
+template <int D>
+__global__ __launch_bounds__(kWaves * 64) void k_score_topk_wide(
+    const float* __restrict__ uemb, int64_t ld_u, const int32_t* __restrict__ users,
+    int32_t n_users, const float* __restrict__ iemb, int64_t ld_i, int32_t n_items,
+    int32_t split_len, const int32_t* __restrict__ mrow, const int32_t* __restrict__ mitems, int K,
+    int cap, float* cand_s, int32_t* cand_i, int32_t* __restrict__ part_cnt) {
+    constexpr int DH = D / 2;
+    // per wave: WideState | cap scores | cap indices
+    extern __shared__ __attribute__((aligned(16))) char wsm[];
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    char* mine = wsm + (size_t)wave * (sizeof(WideState) + (size_t)cap * 8);
+    WideState& st = *reinterpret_cast<WideState*>(mine);
+    float* ss = reinterpret_cast<float*>(mine + sizeof(WideState));
+    int32_t* si = reinterpret_cast<int32_t*>(ss + cap);
+    const int32_t ub = (blockIdx.x * kWaves + wave) * kUsersPerWave;
+    const int32_t split = blockIdx.y;
+    const int32_t it0 = split * split_len;
+    const int32_t it1 = min(n_items, it0 + split_len);
+    // row r of this wave: buffer (split, ub + r), cap entries (only slots < n_users are touched)
+    const int64_t buf0 = ((int64_t)split * n_users + ub) * cap;
+
+    if (lane < kUsersPerWave) {
+        st.cnt[lane] = 0;
+        st.thr[lane] = -INFINITY;
+    }
+    float4 a[D / 8];
+    {
+        const bool ok = ub + col < n_users;
+        load_row_half<D>(uemb + (ok ? (int64_t)users[ub + col] * ld_u : 0) + h * DH, ok, a);
+    }
+    if (lane < kUsersPerWave) {
+        const bool ok = ub + lane < n_users;
+        const int32_t u = ok ? users[ub + lane] : 0;
+        st.mlo[lane] = ok ? mrow[u] : 0;
+        st.mhi[lane] = ok ? mrow[u + 1] : -1;
+    }
+    wave_sync();
+    float4 bcur[D / 8], bnxt[D / 8];
+    auto load_tile = [&](int32_t t0, float4 (&b)[D / 8]) {
+        const int32_t item = t0 + col;
+        const bool iok = item < it1;
+        load_row_half<D>(iemb + (iok ? (int64_t)item * ld_i : 0) + h * DH, iok, b);
+    };
+    if (it0 < it1) load_tile(it0, bcur);
+    for (int32_t t0 = it0; t0 < it1; t0 += 32) {
+        if (t0 + 32 < it1) load_tile(t0 + 32, bnxt);
+        const int32_t item = t0 + col;
+        const bool iok = item < it1;
+        const f32x16 acc = score_tile<D>(a, bcur);
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = c_row(r, h);
+            float sc = acc[r];
+            const float thr = st.thr[row];
+            if (iok && sc > thr) {
+                const int32_t lo = st.mlo[row], hi = st.mhi[row];
+                if (hi >= lo) {
+                    if (in_sorted(mitems, lo, hi, item)) sc = kMasked;  // main.py:422-424
+                    if (sc > thr) {
+                        const int pos = atomicAdd(&st.cnt[row], 1);
+                        if (pos < cap) {  // (always: at most cap - 32 before a tile, 32 a tile)
+                            cand_s[buf0 + (int64_t)row * cap + pos] = sc;
+                            cand_i[buf0 + (int64_t)row * cap + pos] = item;
+                        }
+                        any = true;
+                    }
+                }
+            }
+        }
+        wave_sync();
+        if (__any(any)) {
+            // select every user whose buffer could overflow on the next tile
+            uint64_t need = __ballot(lane < kUsersPerWave && st.cnt[lane] > cap - 32);
+            while (need) {
+                const int u = __builtin_ctzll(need);
+                need &= need - 1;
+                wide_select(st, ss, si, cand_s + buf0 + (int64_t)u * cap,
+                            cand_i + buf0 + (int64_t)u * cap, u, K, cap, lane);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < D / 8; ++q) bcur[q] = bnxt[q];
+    }
+    // final: every buffer's first cnt entries become the split's sorted list
+    for (int u = 0; u < kUsersPerWave; ++u) {
+        if (ub + u >= n_users) break;
+        wide_select(st, ss, si, cand_s + buf0 + (int64_t)u * cap, cand_i + buf0 + (int64_t)u * cap,
+                    u, K, cap, lane);
+        if (lane == 0) part_cnt[(int64_t)split * n_users + ub + u] = st.cnt[u];
+    }
+}
+
+// The number of entries of the sorted list (ls, li)[0, n) that beat (s, x).
+__device__ __forceinline__ int wide_place(const float* __restrict__ ls,
+                                          const int32_t* __restrict__ li, int n, float s,
+                                          int32_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (better(ls[mid], li[mid], s, x)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kWideMergeThreads) void k_topk_wide_merge(
+    const float* __restrict__ cand_s, const int32_t* __restrict__ cand_i,
+    const int32_t* __restrict__ part_cnt, int32_t n_users, int32_t n_splits, int K, int cap,
+    float* __restrict__ top_s, int32_t* __restrict__ top_i) {
+    __shared__ int32_t s_cnt[256];  // n_splits <= 256
+    __shared__ float s_t[kWideMergeThreads / 64];
+    __shared__ int32_t s_tot[kWideMergeThreads / 64];
+    const int32_t slot = blockIdx.x;
+    const int tid = threadIdx.x;
+    float t = -INFINITY;
+    int32_t tot = 0;
+    for (int s = tid; s < n_splits; s += kWideMergeThreads) {
+        const int64_t b = ((int64_t)s * n_users + slot) * cap;
+        const int32_t c = min(max(part_cnt[(int64_t)s * n_users + slot], 0), K);
+        s_cnt[s] = c;
+        tot += c;
+        if (c == K) t = fmaxf(t, cand_s[b + K - 1]);  // a full list bounds the global K-th score
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        t = fmaxf(t, __shfl_xor(t, off));
+        tot += __shfl_xor(tot, off);
+    }
+    if ((tid & 63) == 0) {
+        s_t[tid >> 6] = t;
+        s_tot[tid >> 6] = tot;
+    }
+    __syncthreads();
+    t = s_t[0];
+    tot = s_tot[0];
+#pragma unroll
+    for (int w = 1; w < kWideMergeThreads / 64; ++w) {
+        t = fmaxf(t, s_t[w]);
+        tot += s_tot[w];
+    }
+    const int total = n_splits * K;  // <= 256 * 1024
+    for (int e = tid; e < total; e += kWideMergeThreads) {
+        const int s = e / K, j = e - s * K;
+        if (j >= s_cnt[s]) continue;
+        const int64_t b = ((int64_t)s * n_users + slot) * cap;
+        const float v = cand_s[b + j];
+        if (!(v >= t)) continue;
+        const int32_t id = cand_i[b + j];
+        int rank = j;
+        for (int s2 = 0; s2 < n_splits && rank < K; ++s2) {
+            if (s2 == s) continue;
+            const int64_t b2 = ((int64_t)s2 * n_users + slot) * cap;
+            rank += wide_place(cand_s + b2, cand_i + b2, s_cnt[s2], v, id);
+        }
+        if (rank < K) {
+            top_s[(int64_t)slot * K + rank] = v;
+            top_i[(int64_t)slot * K + rank] = id;
+        }
+    }
+    for (int r = min(tot, K) + tid; r < K; r += kWideMergeThreads) {  // fewer than K listable items
+        top_s[(int64_t)slot * K + r] = -INFINITY;
+        top_i[(int64_t)slot * K + r] = -1;
+    }
+}
+
+// Scratch: cand score [n_splits x n_users x cap] | cand index, the same | count [n_splits x n_users]
+constexpr size_t wide_bytes(int64_t n_users, int64_t cap, int64_t n_splits) {
+    return ((size_t)n_splits * (size_t)n_users * (size_t)(8 * cap + 4) + 15) / 16 * 16;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lgcn_topk_wide_splits(int32_t n_users, int32_t n_items, int32_t k, int32_t n_cu) {
+    int64_t s = lgcn_eval_splits(n_users, n_items, n_cu);
+    if (k < 1) k = 1;
+    if (k > kWideMaxK) k = kWideMaxK;
+    const int64_t floor_len = 8LL * k > 2048 ? 8LL * k : 2048;
+    const int64_t max_by_len = (int64_t)(n_items > 0 ? n_items : 0) / floor_len;
+    if (s > max_by_len) s = max_by_len;
+    if (s > kWideMergeEntries / k) s = kWideMergeEntries / k;
+    if (s < 1) s = 1;
+    return (int)s;
+}
+
+size_t lgcn_score_topk_wide_scratch_bytes(int32_t n_users, int32_t k, int32_t n_splits) {
+    if (n_users < 0 || k < 1 || k > kWideMaxK || n_splits < 1 || n_splits > 256) return 0;
+    return wide_bytes(n_users, 2 * wide_kp(k), n_splits);
+}
+
+int lgcn_score_topk_wide(const float* user_emb, int64_t ld_u, const int32_t* users,
+                         int32_t n_users, const float* item_emb, int64_t ld_i, int32_t n_items,
+                         int32_t d, const int32_t* mask_rowptr, const int32_t* mask_items,
+                         int32_t k, int32_t n_splits, void* scratch, size_t scratch_bytes,
+                         float* top_scores, int32_t* top_idx, void* stream) {
+    if (k < 1 || k > kWideMaxK) return LGCN_EINVAL;
+    if (const int rc = eval_args(user_emb, ld_u, n_users, item_emb, ld_i, n_items, d, n_splits))
+        return rc;
+    if (n_users == 0) return 0;
+    if (!user_emb || !users || !item_emb || !mask_rowptr || !scratch || !top_scores || !top_idx)
+        return LGCN_EINVAL;
+    const int cap = 2 * wide_kp(k);
+    if (scratch_bytes < wide_bytes(n_users, cap, n_splits)) return LGCN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(scratch) & 3) return LGCN_EALIGN;
+    const size_t n_buf = (size_t)n_splits * (size_t)n_users * (size_t)cap;
+    float* cand_s = static_cast<float*>(scratch);
+    int32_t* cand_i = reinterpret_cast<int32_t*>(cand_s + n_buf);
+    int32_t* part_cnt = cand_i + n_buf;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t split_len = eval_split_len(n_items, n_splits);
+    const dim3 grid(user_tiles(n_users), n_splits);
+    const size_t lds = (sizeof(WideState) + (size_t)cap * 8) * kWaves;
+    hipError_t e = with_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        const hipError_t ea =
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_topk_wide<D>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)((sizeof(WideState) + (size_t)2 * kWideMaxK * 8) * kWaves));
+        if (ea != hipSuccess) return ea;
+        hipLaunchKernelGGL(k_score_topk_wide<D>, grid, dim3(kWaves * 64), lds, s, user_emb, ld_u,
+                           users, n_users, item_emb, ld_i, n_items, split_len, mask_rowptr,
+                           mask_items, k, cap, cand_s, cand_i, part_cnt);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_topk_wide_merge, dim3(n_users), dim3(kWideMergeThreads), 0, s, cand_s,
+                       cand_i, part_cnt, n_users, n_splits, k, cap, top_scores, top_idx);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // extern "C"

@@ -247,6 +247,10 @@ ABI = [
     ("lgcn_score_rank_lists_scratch_bytes", ctypes.c_size_t, [_I32, _I64, _I32]),
     ("lgcn_score_rank_lists", ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I32, _I32, _P, _P, _P,
                                              _P, _I32, _P, ctypes.c_size_t, _P, _P, _P]),
+    ("lgcn_topk_wide_splits", ctypes.c_int, [_I32, _I32, _I32, _I32]),
+    ("lgcn_score_topk_wide_scratch_bytes", ctypes.c_size_t, [_I32, _I32, _I32]),
+    ("lgcn_score_topk_wide", ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I32, _I32, _P, _P, _I32,
+                                            _I32, _P, ctypes.c_size_t, _P, _P, _P]),
     ("lgcn_spmm_layer", ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _P, RowsT, ctypes.c_float,
                                        _P, _P, _I64, _I32, ctypes.POINTER(EpilogueT), _P]),
     ("lgcn_rows_nonzero", ctypes.c_int, [RowsT, _I32, _I32, _P, _P, _P]),

@@ -498,6 +498,161 @@ def metrics_from_rank_lists(ranks, rowptr, ks=(20,)):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# recommendation lists: lgcn_score_topk_wide (the first k items per user for k up to 1024)
+# ----------------------------------------------------------------------------------------------
+# The lists are the ones the rank kernels describe: entry j of a user's list is the item whose
+# lgcn_score_rank rank is j (score descending, item index ascending, the user's mask items at
+# -1e10), positions past the listable items hold -inf / -1.
+WIDE_MAX_K = 1024                 # LGCN_TOPK_WIDE_MAX_K (include/lgcn.h)
+
+
+def wide_supported(d, k):
+    return d in FUSED_DIMS and 1 <= k <= WIDE_MAX_K
+
+
+def _user_ids(name, users, n_table):
+    """users as a host int64 array, every id inside [0, n_table) (ValueError otherwise): the
+    kernels read the rows they are given."""
+    if torch.is_tensor(users):
+        users = users.detach().cpu().numpy()
+    users = np.asarray(users)
+    if users.ndim != 1:
+        raise ValueError(f"{name}: users must be 1-D")
+    if users.size and users.dtype.kind not in "iu":
+        raise engine.LgcnError(f"{name}: users must be integers, not {users.dtype}")
+    users = users.astype(np.int64)
+    if users.size and (users.min() < 0 or users.max() >= n_table):
+        raise ValueError(f"{name}: a user id lies outside [0, {n_table})")
+    return users
+
+
+def _wide_launch(ue, ie, users, mrow, mit, k, n_splits, scratch, top_s, top_i):
+    """One lgcn_score_topk_wide on prepared device tensors (int32 users [n > 0], outputs [n x k],
+    a uint8 scratch), on the current stream."""
+    lib = engine.load_library()
+    dev = ie.device
+    P = engine._ptr
+    with torch.cuda.device(dev):
+        engine._check(lib.lgcn_score_topk_wide(
+            P(ue), ue.stride(0), P(users), int(users.numel()), P(ie), ie.stride(0),
+            int(ie.shape[0]), int(ie.shape[1]), P(mrow), P(mit), k, n_splits, P(scratch),
+            int(scratch.numel()), P(top_s), P(top_i), engine._stream(dev)), "lgcn_score_topk_wide")
+
+
+def _wide_batches(ue, ie, users, mrow, mit, k, batch_size):
+    """(scores fp32 [n x k], items int32 [n x k]): one lgcn_score_topk_wide per batch_size slots
+    on views of the device-resident int32 users, one scratch (sized by the library) for the
+    largest batch. No read-back."""
+    lib = engine.load_library()
+    dev = ie.device
+    n, n_items = int(users.numel()), int(ie.shape[0])
+    top_s = torch.empty((n, k), dtype=torch.float32, device=dev)
+    top_i = torch.empty((n, k), dtype=torch.int32, device=dev)
+    if n == 0:
+        return top_s, top_i
+    cus = _device_cus(dev)
+    sizes = sorted({min(batch_size, n), n % batch_size or min(batch_size, n)})
+    splits = {b: lib.lgcn_topk_wide_splits(b, n_items, k, cus) for b in sizes}
+    scratch = torch.empty(max(lib.lgcn_score_topk_wide_scratch_bytes(b, k, s)
+                              for b, s in splits.items()), dtype=torch.uint8, device=dev)
+    ue, ie = _rows(ue), _rows(ie)
+    for s in range(0, n, batch_size):
+        e = min(s + batch_size, n)
+        _wide_launch(ue, ie, users[s:e], mrow, mit, k, splits[e - s], scratch, top_s[s:e],
+                     top_i[s:e])
+    return top_s, top_i
+
+
+def topk_wide(user_emb, item_emb, users, mask_rowptr, mask_items, k):
+    """(scores fp32 [n x k], items int32 [n x k]) on the tables' HIP device: lgcn_score_topk_wide
+    for the batch slots users[b], one launch. Every id must be a row of user_emb (ValueError). The
+    mask arrays as for rank_fused. A width or k the kernel does not have is an error
+    (topk_total_order_torch takes any)."""
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    k = int(k)
+    if dev.type != "cuda":
+        raise engine.LgcnError("topk_wide needs tables on a HIP device (topk_total_order_torch "
+                               "runs anywhere)")
+    if not wide_supported(item_emb.shape[1], k):
+        raise engine.LgcnError(f"topk_wide: d = {item_emb.shape[1]}, k = {k} outside "
+                               f"{FUSED_DIMS} x [1, {WIDE_MAX_K}]")
+    mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev)
+    mit = _mask_tensor("mask_items", mask_items, dev)
+    if mrow.numel() != user_emb.shape[0] + 1:
+        raise ValueError("topk_wide: mask_rowptr must hold one entry per user row and one more")
+    ids = _user_ids("topk_wide", users, user_emb.shape[0])
+    users = torch.from_numpy(ids.astype(np.int32)).to(dev)
+    return _wide_batches(user_emb, item_emb, users, mrow, _items_to_pass(mit), k,
+                         max(int(users.numel()), 1))
+
+
+def topk_total_order_torch(user_emb, item_emb, users, mask_rowptr, mask_items, k,
+                           batch_size=1024):
+    """topk_wide's contract with torch ops, for any width, any k >= 1 and any device (CPU
+    included): scores by matmul in chunks of at most 1024 users, the user's mask items set to
+    -1e10, the first k of a stable descending sort (equal scores keep ascending item index),
+    -inf / -1 past the listable items. Its scores are matmul's, so on rounded inputs a list may
+    differ from the kernel's where two scores meet in the last bit."""
+    _check_tables(user_emb, item_emb)
+    dev = item_emb.device
+    k = int(k)
+    if k < 1:
+        raise ValueError("topk_total_order_torch: k must be positive")
+    n_table, n_items = user_emb.shape[0], item_emb.shape[0]
+    mrow = _mask_tensor("mask_rowptr", mask_rowptr, dev).long()
+    mit = _mask_tensor("mask_items", mask_items, dev).long()
+    if mrow.numel() != n_table + 1:
+        raise ValueError("topk_total_order_torch: mask_rowptr must hold one entry per user row "
+                         "and one more")
+    users = torch.from_numpy(_user_ids("topk_total_order_torch", users, n_table)).to(dev)
+    n = int(users.numel())
+    top_s = torch.full((n, k), float("-inf"), dtype=torch.float32, device=dev)
+    top_i = torch.full((n, k), -1, dtype=torch.int32, device=dev)
+    if n == 0 or n_items == 0:
+        return top_s, top_i
+    batch_size = max(1, min(int(batch_size), 1024))
+    kk = min(k, n_items)
+    for s in range(0, n, batch_size):
+        u = users[s:s + batch_size]
+        scores = torch.matmul(user_emb[u], item_emb.T)
+        lens = mrow[u + 1] - mrow[u]
+        total = int(lens.sum())
+        if total:
+            rr = torch.repeat_interleave(torch.arange(len(u), device=dev), lens)
+            first = torch.cumsum(lens, 0) - lens
+            pos = torch.arange(total, device=dev) - first[rr] + mrow[u][rr]
+            scores[rr, mit[pos]] = -1e10
+        # a NaN is never listed (and -inf is what an empty position holds)
+        scores.masked_fill_(torch.isnan(scores), float("-inf"))
+        vals, idx = torch.sort(scores, dim=1, descending=True, stable=True)
+        vals, idx = vals[:, :kk], idx[:, :kk]
+        listed = vals > float("-inf")
+        top_s[s:s + batch_size, :kk] = vals
+        top_i[s:s + batch_size, :kk] = torch.where(listed, idx, torch.full_like(idx, -1)).int()
+    return top_s, top_i
+
+
+def similar_items(item_emb, items, k):
+    """Item-to-item lists: (scores fp32 [n x k], items int32 [n x k]) on item_emb's device, the k
+    items with the largest dot product with each query item, the query itself excluded (it counts
+    at -1e10, as a user's train items do). The query table is the item table and the mask of row i
+    is {i}. HIP tables with wide_supported run lgcn_score_topk_wide (no fallback from it),
+    anything else the torch route."""
+    if not torch.is_tensor(item_emb) or item_emb.dim() != 2:
+        raise engine.LgcnError("similar_items: item_emb must be a 2-D float32 tensor")
+    _check_tables(item_emb, item_emb)
+    dev = item_emb.device
+    k = int(k)
+    n_items = item_emb.shape[0]
+    rowptr = torch.arange(n_items + 1, dtype=torch.int32, device=dev)
+    own = torch.arange(n_items, dtype=torch.int32, device=dev)
+    if item_emb.is_cuda and wide_supported(item_emb.shape[1], k):
+        return topk_wide(item_emb, item_emb, items, rowptr, own, k)
+    return topk_total_order_torch(item_emb, item_emb, items, rowptr, own, k)
+
+
 class Evaluator:
     """Evaluator(train_users, train_items, num_users, num_items, device)
 
@@ -508,6 +663,7 @@ class Evaluator:
         ev = Evaluator.from_sampler(sampler)          # or Evaluator(train_u, train_i, U, I, dev)
         metrics = ev.evaluate(model, adj, val_df, ks=(10, 20, 50))
         metrics = ev.evaluate_lists(model, adj, test_df, ks=(10, 20, 50))  # every row of the frame
+        scores, items = ev.recommend(model, adj, users, k=100)      # the lists, k up to WIDE_MAX_K
 
     evaluate() keeps one held-out item per user (the last row of a user wins, as main.py's
     dict(zip(...))); evaluate_lists() keeps them all and ranks a user's whole list from one pass.
@@ -656,6 +812,32 @@ class Evaluator:
                 _rank_lists_launch(ue, ie, users_t[s:e], rowptr_t[s:e + 1], items_t, self._rowptr,
                                    self._items, rank, score, scratch, splits[e - s])
         return eu, rowptr, rank
+
+    def recommend(self, model, adj, users, k, batch_size=8192, exclude_train=True):
+        """The k best items of every user of `users` in rank order: (scores fp32 [n x k], items
+        int32 [n x k]) on the evaluator's device, -inf / -1 past the listable items. One
+        propagation under no_grad in model.eval(), the ids checked on the host (one outside
+        [0, num_users) is a ValueError) and uploaded once, then one lgcn_score_topk_wide per batch
+        on views of them. No read-back. exclude_train=False lists the train items too (an
+        all-empty mask). HIP tables with wide_supported(d, k) run the kernel (no fallback from
+        it), anything else topk_total_order_torch."""
+        batch_size, k = int(batch_size), int(k)
+        if batch_size < 1:
+            raise ValueError("Evaluator.recommend: batch_size must be positive")
+        if k < 1:
+            raise ValueError("Evaluator.recommend: k must be positive")
+        ids = _user_ids("Evaluator.recommend", users, self.num_users)
+        with torch.no_grad():
+            ue, ie = self._tables(model, adj)
+            if exclude_train:
+                mrow, mit = self._rowptr, self._items
+            else:
+                mrow = torch.zeros(self.num_users + 1, dtype=torch.int32, device=self.device)
+                mit = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if not (ie.is_cuda and wide_supported(ie.shape[1], k)):
+                return topk_total_order_torch(ue, ie, ids, mrow, mit, k, min(batch_size, 1024))
+            users_t = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            return _wide_batches(ue, ie, users_t, mrow, mit, k, batch_size)
 
     def evaluate_lists(self, model, adj, eval_data, ks=(20,)):
         """metrics_from_rank_lists of rank_lists(): eval_data is a (users, items) pair, or a

@@ -60,8 +60,9 @@ extern "C" {
  * (lgcn_bpr_brand_loss, lgcn_bpr_brand_loss_indexed, lgcn_bpr_brand_keys) and the fusion pre-layer's
  * backward (lgcn_fusion_prelayer_backward, its scratch query, LGCN_FUSION_BWD_CHUNK,
  * LGCN_TUNE_FUSION_BWD_BLOCKS) and the Adam step (lgcn_adam_step, lgcn_adam_chunks, their two
- * structs, LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK) were added without a bump:
- * purely additive, no existing symbol, struct or constant changed. */
+ * structs, LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK) and the wide recommendation lists
+ * (lgcn_score_topk_wide, lgcn_topk_wide_splits, its scratch query, LGCN_TOPK_WIDE_MAX_K) were
+ * added without a bump: purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -985,6 +986,44 @@ int lgcn_score_rank_lists(const float* user_emb, int64_t ld_u, const int32_t* us
                           const int32_t* target_rowptr, const int32_t* target_items,
                           int32_t n_splits, void* scratch, size_t scratch_bytes,
                           float* target_score, int32_t* rank, void* stream);
+
+/* Recommendation lists: lgcn_score_topk's lists for k in [1, LGCN_TOPK_WIDE_MAX_K], still without
+ * the [n_users x n_items] score matrix. For slot b with u = users[b], top_idx[b][j] is the item t
+ * for which lgcn_score_rank gives rank j for the slot (u, t), for every j < k, and top_scores[b][j]
+ * is that call's target_score, bit for bit: every score that enters a comparison is the MFMA
+ * tile's value for its (user row, item row) pair, u's mask items count at fp32(-1e10) (a value,
+ * not a sentinel: an unmasked item scoring below it ranks after the masked ones), and the order
+ * is score descending, item index ascending. Positions past the number of listable items hold
+ * -inf / -1. An item whose score is a NaN (or -inf) is never listed, as in lgcn_score_topk. For
+ * k <= 32 both outputs equal lgcn_score_topk's as raw bits. The result does not depend on
+ * n_splits, the slot's place in the batch, the launch geometry or the run. users[b] must be a
+ * valid row, as for lgcn_score_topk; a user may appear in several slots, and user_emb may be
+ * item_emb.
+ * A user's candidates (scores above its current k-th best) are kept per (split, slot) in scratch,
+ * 2 kp entries with kp the power of two >= max(k, 32); a buffer that could overflow on the next
+ * 32-item tile is sorted in LDS (bitonic, at most 2048 pairs per wave) and cut to its k best. The
+ * splits' sorted lists are merged by rank: an entry's place is the sum of its binary-search
+ * places in the splits' lists.
+ * scratch: lgcn_score_topk_wide_scratch_bytes(n_users, k, n_splits) bytes, 4-B aligned, contents
+ * opaque: n_splits * n_users * (16 kp + 4) rounded up to 16 (0 for arguments out of range).
+ * lgcn_topk_wide_splits: lgcn_eval_splits(n_users, n_items, n_cu), capped so that (a) with more
+ * than one split n_items / n_splits >= max(2048, 8 k): a split is several times k long and its
+ * list is not most of the split, and (b) n_splits * k <= 16384: the merge stays small. Always in
+ * [1, 256]; never grows with n_users. Any n_splits in [1, 256] gives the same lists.
+ * Checks, in this order, on the host before any launch: k outside [1, LGCN_TOPK_WIDE_MAX_K]
+ * (LGCN_EINVAL); then d, alignment, strides and n_splits in [1, 256] as lgcn_score_rank's; then
+ * n_users == 0 returns 0 and touches no pointer (all may be NULL); then a NULL pointer (mask_items
+ * may be NULL when every list is empty) or scratch_bytes below the stated size (LGCN_EINVAL); then
+ * a scratch that is not 4-B aligned (LGCN_EALIGN). Allocates nothing, never synchronises, reads
+ * nothing back, everything on `stream` (capture-safe). */
+#define LGCN_TOPK_WIDE_MAX_K 1024
+int lgcn_topk_wide_splits(int32_t n_users, int32_t n_items, int32_t k, int32_t n_cu);
+size_t lgcn_score_topk_wide_scratch_bytes(int32_t n_users, int32_t k, int32_t n_splits);
+int lgcn_score_topk_wide(const float* user_emb, int64_t ld_u, const int32_t* users,
+                         int32_t n_users, const float* item_emb, int64_t ld_i, int32_t n_items,
+                         int32_t d, const int32_t* mask_rowptr, const int32_t* mask_items,
+                         int32_t k, int32_t n_splits, void* scratch, size_t scratch_bytes,
+                         float* top_scores, int32_t* top_idx, void* stream);
 
 /* ---- optimizer (main.py's torch.optim.Adam(model.parameters(), lr)) ------------------------- */
 /* One Adam step over up to LGCN_ADAM_MAX_TENSORS fp32 tensors in ONE launch, bit for bit what

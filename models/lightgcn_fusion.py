@@ -93,6 +93,11 @@ class LightGCN_Fusion(nn.Module):
         (evaluate.Evaluator.evaluate_lists: all (user, item) rows are kept, one read-back)."""
         return evaluator.evaluate_lists(self, adj, (eval_users, eval_items), ks)
 
+    def recommend(self, adj, users, k, evaluator, batch_size=8192, exclude_train=True):
+        """The k best items per user in rank order, (scores fp32, items int32) [n x k] on the
+        device, for k up to evaluate.WIDE_MAX_K on the kernel (evaluate.Evaluator.recommend)."""
+        return evaluator.recommend(self, adj, users, k, batch_size, exclude_train)
+
     def set_graph(self, adj_mat):
         self._graph_adj = adj_mat
         return self
