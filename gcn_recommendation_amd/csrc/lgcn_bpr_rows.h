@@ -1,7 +1,8 @@
 // lgcn_bpr_rows.h — the BPR batch kernels shared by lgcn_bpr.hip (rows given as gathered
 // [B x d] blocks) and lgcn_bpr_step.hip (rows read from the tables by index): one row kernel,
 // templated on how sample b's six row pointers are obtained, and the fixed-order batch reduction;
-// below them their siblings with the brand-preference term (eight rows per sample).
+// below them their siblings with the brand-preference term (eight rows per sample). row_scores,
+// how all of them form a score, is also what lgcn_bpr_select_hardest ranks candidates by.
 //
 //   loss = -mean_b log(sigmoid(<u_b,p_b> - <u_b,n_b>) + 1e-8)
 //          + lambda * (|U0|^2 + |P0|^2 + |N0|^2) / B
@@ -67,6 +68,24 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// The scores s[i] = <u, v[i]> of one user row against N item (or brand) rows, the one statement of
+// how a batch kernel forms a score: per lane an fmaf chain over k = lane, lane + 64, ... from +0,
+// then wave_sum; every lane returns the sum. A score is a function of its two rows alone: N only
+// sets how many rows' loads are in flight.
+template <int N>
+__device__ __forceinline__ void row_scores(const float* u, const float* const (&v)[N], int32_t d,
+                                           int lane, float (&s)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = 0.f;
+    for (int k = lane; k < d; k += kWave) {
+        const float x = u[k];
+#pragma unroll
+        for (int i = 0; i < N; ++i) s[i] = __builtin_fmaf(x, v[i][k], s[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = wave_sum(s[i]);
+}
+
 // grads = [6 x B x d] (u, p, n, u0, p0, n0); terms = [2 x B] (log term, squared norms). A sample
 // without rows (Rows::get false) contributes zero terms and zero gradient rows.
 template <typename Rows>
@@ -98,19 +117,17 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_bpr_rows(
     const float* ub0 = sr.r[3];
     const float* pb0 = sr.r[4];
     const float* nb0 = sr.r[5];
-    float sp = 0.f, sn = 0.f, sq = 0.f;
+    float sq = 0.f;
     for (int k = lane; k < d; k += kWave) {
-        const float x = ub[k];
-        sp = __builtin_fmaf(x, pb[k], sp);
-        sn = __builtin_fmaf(x, nb[k], sn);
         sq = __builtin_fmaf(ub0[k], ub0[k], sq);
         sq = __builtin_fmaf(pb0[k], pb0[k], sq);
         sq = __builtin_fmaf(nb0[k], nb0[k], sq);
     }
-    sp = wave_sum(sp);
-    sn = wave_sum(sn);
+    const float* const pn[2] = {pb, nb};
+    float sc[2];  // sp, sn
+    row_scores(ub, pn, d, lane, sc);
     sq = wave_sum(sq);
-    const float x = sp - sn;
+    const float x = sc[0] - sc[1];
     const float s = 1.f / (1.f + expf(-x));
     const float c = ((-1.f / (float)B) / (s + 1e-8f)) * (1.f - s) * s;
     const float r = 2.f * lambda / (float)B;
@@ -259,24 +276,21 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_bpr_brand_rows(
     const float* nb0 = sr.r[5];
     const float* bpb = sr.r[6];  // read only when brand
     const float* bnb = sr.r[7];
-    float sp = 0.f, sn = 0.f, sq = 0.f, tp = 0.f, tn = 0.f;
+    float sq = 0.f;
     for (int k = lane; k < d; k += kWave) {
-        const float x = ub[k];
-        sp = __builtin_fmaf(x, pb[k], sp);
-        sn = __builtin_fmaf(x, nb[k], sn);
         sq = __builtin_fmaf(ub0[k], ub0[k], sq);
         sq = __builtin_fmaf(pb0[k], pb0[k], sq);
         sq = __builtin_fmaf(nb0[k], nb0[k], sq);
-        if (brand) {
-            tp = __builtin_fmaf(x, bpb[k], tp);
-            tn = __builtin_fmaf(x, bnb[k], tn);
-        }
     }
-    sp = wave_sum(sp);
-    sn = wave_sum(sn);
+    const float* const pn[2] = {pb, nb};
+    float sc[2], tc[2] = {0.f, 0.f};  // sp, sn and tp, tn
+    row_scores(ub, pn, d, lane, sc);
+    if (brand) {  // uniform over the wave: one sample per wave
+        const float* const bpn[2] = {bpb, bnb};
+        row_scores(ub, bpn, d, lane, tc);
+    }
     sq = wave_sum(sq);
-    tp = wave_sum(tp);
-    tn = wave_sum(tn);
+    const float sp = sc[0], sn = sc[1], tp = tc[0], tn = tc[1];
     const float x = sp - sn;
     const float s = 1.f / (1.f + expf(-x));
     const float c = ((-1.f / (float)B) / (s + 1e-8f)) * (1.f - s) * s;

@@ -1,6 +1,8 @@
 // lgcn_bpr_step.hip — the pieces of a fused BPR training step that know the batch indices
 // (main.py:495-525 without autograd's six gathers and six dense IndexBackward blocks):
 //   lgcn_bpr_loss_indexed  the BPR + L2 loss of lgcn_bpr_loss, rows read from the tables by index
+//   lgcn_bpr_select_hardest  per sample the highest-scoring of n_neg candidate negatives, scored
+//                          by the loss kernel's own expression: the step then trains on it
 //   lgcn_bpr_keys          the 3B destination keys of a batch's per-sample gradient rows
 //   lgcn_bpr_brand_loss_indexed / lgcn_bpr_brand_keys   both with the brand-preference term: the
 //                          brand rows found through a device-resident item -> brand map, 5B keys
@@ -64,6 +66,59 @@ __global__ __launch_bounds__(256) void k_bpr_brand_keys(
     keys[2 * (int64_t)B + b] = ok ? 2 * (n_users + in) + 1 : none;
     keys[3 * (int64_t)B + b] = brand ? 2 * (first + rp) : none;
     keys[4 * (int64_t)B + b] = brand ? 2 * (first + rn) + 1 : none;
+}
+
+constexpr int kSelectRows = 4;  // candidate rows whose loads are in flight together
+
+// One wave per sample: the hardest of its n_neg candidates (include/lgcn.h states the rule). Lane
+// m holds candidate m's index, so the indices are gathered before the first row load; the valid
+// ones are then scored kSelectRows at a time, in ascending ordinal, by the loss kernel's own
+// row_scores. A short last group repeats its first candidate and does not compare the repeats.
+__global__ __launch_bounds__(kWave * lgcn_bpr::kRowsPerBlock) void k_bpr_select_hardest(
+    const float* __restrict__ fu, int64_t ld_fu, const float* __restrict__ fi, int64_t ld_fi,
+    int64_t n_users, int64_t n_items, const int64_t* __restrict__ users,
+    const int64_t* __restrict__ cand, int32_t B, int32_t n_neg, int32_t d,
+    int64_t* __restrict__ neg_out, float* __restrict__ score_out) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t b = (int64_t)blockIdx.x * lgcn_bpr::kRowsPerBlock + threadIdx.x / kWave;
+    if (b >= B) return;
+    const int64_t iu = users[b];
+    const int64_t mine = lane < n_neg ? cand[b * n_neg + lane] : -1;
+    const bool ok = iu >= 0 && iu < n_users && mine >= 0 && mine < n_items;
+    uint64_t todo = __ballot(ok);
+    int64_t best = -1;
+    float best_s = __builtin_nanf("");
+    if (todo != 0) {
+        const float* ub = fu + iu * ld_fu;
+        while (todo != 0) {
+            int64_t item[kSelectRows];
+            const float* rows[kSelectRows];
+            int n = 0;
+#pragma unroll
+            for (int i = 0; i < kSelectRows; ++i) {
+                if (todo != 0) {  // uniform over the wave; true for i = 0
+                    item[i] = __shfl(mine, __builtin_ctzll(todo), kWave);  // ascending ordinal
+                    todo &= todo - 1;
+                    n = i + 1;
+                } else {
+                    item[i] = item[0];
+                }
+                rows[i] = fi + item[i] * ld_fi;
+            }
+            float sc[kSelectRows];
+            lgcn_bpr::row_scores(ub, rows, d, lane, sc);
+#pragma unroll
+            for (int i = 0; i < kSelectRows; ++i)
+                if (i < n && (best < 0 || sc[i] > best_s)) {
+                    best = item[i];
+                    best_s = sc[i];
+                }
+        }
+    }
+    if (lane == 0) {
+        neg_out[b] = best;
+        if (score_out != nullptr) score_out[b] = best_s;
+    }
 }
 
 // One wave per sorted position; the wave at the head of a run of equal rows (key >> 1) walks the
@@ -157,6 +212,22 @@ int lgcn_bpr_keys(const int64_t* users, const int64_t* pos, const int64_t* neg, 
     hipLaunchKernelGGL(k_bpr_keys, dim3((uint32_t)(((int64_t)B + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), users, pos, neg, B, n_users, n_items,
                        keys);
+    return last_err();
+}
+
+int lgcn_bpr_select_hardest(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                            int64_t n_users, int64_t n_items, const int64_t* users,
+                            const int64_t* cand, int32_t B, int32_t n_neg, int32_t d,
+                            int64_t* neg_out, float* score_out, void* stream) {
+    if (B < 0 || d < 1 || n_neg < 1 || n_neg > LGCN_BPR_MAX_NEG) return LGCN_EINVAL;
+    if (ld_fu < d || ld_fi < d || n_users < 0 || n_items < 0) return LGCN_EINVAL;
+    if (B == 0) return 0;
+    if (!fu || !fi || !users || !cand || !neg_out) return LGCN_EINVAL;
+    const int64_t grid = ((int64_t)B + lgcn_bpr::kRowsPerBlock - 1) / lgcn_bpr::kRowsPerBlock;
+    hipLaunchKernelGGL(k_bpr_select_hardest, dim3((uint32_t)grid),
+                       dim3(kWave * lgcn_bpr::kRowsPerBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), fu, ld_fu, fi, ld_fi, n_users,
+                       n_items, users, cand, B, n_neg, d, neg_out, score_out);
     return last_err();
 }
 

@@ -1,6 +1,7 @@
 // lgcn_sampler.hip — the BPR negative sampler (main.py:349-363, BPRDataset.__getitem__) on the
 // device: lgcn_bpr_sample writes the (user, positive, negative) triples of a run of interactions,
-// a whole epoch in one launch. Declared in include/lgcn.h, which defines the draw.
+// a whole epoch in one launch; lgcn_bpr_sample_multi writes n_neg negatives per triple (ordinal m
+// = the same draw with counter word 3 = m). Declared in include/lgcn.h, which defines the draw.
 //
 // The negative of interaction idx is a pure function of (seed, epoch, idx, the user's positive
 // list, n_items): 64 Philox4x32-10 bits -> j = mulhi64(r64, n_free) -> the j-th item missing from
@@ -46,6 +47,26 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     o1 = c1;
 }
 
+// One ordinal's draw for interaction idx of a user with n_free > 0 free items and the sorted
+// positives L [deg]: counter (idx_lo32, idx_hi32, epoch, ordinal).
+__device__ __forceinline__ int64_t draw_negative(int64_t idx, uint32_t epoch, uint32_t ordinal,
+                                                 uint32_t seed_lo, uint32_t seed_hi,
+                                                 int32_t n_free, const int32_t* __restrict__ L,
+                                                 int32_t deg) {
+    uint32_t r0, r1;
+    philox4x32_10((uint32_t)idx, (uint32_t)((uint64_t)idx >> 32), epoch, ordinal, seed_lo, seed_hi,
+                  r0, r1);
+    const uint64_t r64 = ((uint64_t)r1 << 32) | r0;
+    const int32_t j = (int32_t)__umul64hi(r64, (uint64_t)n_free);
+    int32_t lo = 0, hi = deg;  // m = the first t with L[t] - t > j
+    while (lo < hi) {
+        const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
+        if (L[mid] - mid <= j) lo = mid + 1;
+        else hi = mid;
+    }
+    return (int64_t)j + lo;
+}
+
 __global__ __launch_bounds__(kBlock) void k_bpr_sample(
     const int32_t* __restrict__ inter_user, const int32_t* __restrict__ inter_item,
     int64_t n_inter, const int64_t* __restrict__ order, int64_t first, int64_t count,
@@ -67,19 +88,8 @@ __global__ __launch_bounds__(kBlock) void k_bpr_sample(
                 const int32_t n_free = n_items - deg;
                 // deg < 0 or beg < 0: not a row of a CSR; treated as a user without a free item
                 if (beg >= 0 && deg >= 0 && n_free > 0) {
-                    uint32_t r0, r1;
-                    philox4x32_10((uint32_t)idx, (uint32_t)((uint64_t)idx >> 32), epoch, 0u,
-                                  seed_lo, seed_hi, r0, r1);
-                    const uint64_t r64 = ((uint64_t)r1 << 32) | r0;
-                    const int32_t j = (int32_t)__umul64hi(r64, (uint64_t)n_free);
-                    const int32_t* __restrict__ L = pos_items + beg;
-                    int32_t lo = 0, hi = deg;  // m = the first t with L[t] - t > j
-                    while (lo < hi) {
-                        const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-                        if (L[mid] - mid <= j) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    on = (int64_t)j + lo;
+                    on = draw_negative(idx, epoch, 0u, seed_lo, seed_hi, n_free,
+                                       pos_items + beg, deg);
                 } else if (n_unsampled != nullptr) {
                     atomicAdd(n_unsampled, 1);
                 }
@@ -88,6 +98,41 @@ __global__ __launch_bounds__(kBlock) void k_bpr_sample(
         users[s] = ou;
         pos[s] = op;
         neg[s] = on;
+    }
+}
+
+// k_bpr_sample with n_neg independent ordinals per slot: the slot's idx, user, beg and deg are
+// loaded once, its n_neg negatives written side by side (neg [count x n_neg]).
+__global__ __launch_bounds__(kBlock) void k_bpr_sample_multi(
+    const int32_t* __restrict__ inter_user, const int32_t* __restrict__ inter_item,
+    int64_t n_inter, const int64_t* __restrict__ order, int64_t first, int64_t count,
+    const int32_t* __restrict__ pos_rowptr, const int32_t* __restrict__ pos_items,
+    int32_t n_users, int32_t n_items, uint32_t seed_lo, uint32_t seed_hi, uint32_t epoch,
+    int32_t n_neg, int64_t* __restrict__ users, int64_t* __restrict__ pos,
+    int64_t* __restrict__ neg, int32_t* __restrict__ n_unsampled) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < count; s += stride) {
+        const int64_t idx = order != nullptr ? order[first + s] : first + s;
+        int64_t ou = -1, op = -1;
+        int32_t beg = 0, deg = 0, n_free = 0;  // n_free stays 0: every ordinal of the slot is -1
+        if (idx >= 0 && idx < n_inter) {
+            const int32_t u = inter_user[idx];
+            if (u >= 0 && u < n_users) {
+                ou = u;
+                op = inter_item[idx];
+                beg = pos_rowptr[u];
+                deg = pos_rowptr[u + 1] - beg;
+                if (beg >= 0 && deg >= 0 && n_items - deg > 0) n_free = n_items - deg;
+                else if (n_unsampled != nullptr) atomicAdd(n_unsampled, 1);  // once per slot
+            }
+        }
+        users[s] = ou;
+        pos[s] = op;
+        int64_t* __restrict__ out = neg + s * n_neg;
+        for (int32_t m = 0; m < n_neg; ++m)
+            out[m] = n_free > 0 ? draw_negative(idx, epoch, (uint32_t)m, seed_lo, seed_hi, n_free,
+                                                pos_items + beg, deg)
+                                : -1;
     }
 }
 
@@ -109,6 +154,19 @@ int cu_count(int* n_cu) {
     return 0;
 }
 
+// the grid of `count` slots: a block per 256, at most LGCN_TUNE_SAMPLE_BLOCKS (default: 8 per CU)
+int sample_blocks(int64_t count, int64_t* blocks) {
+    int64_t cap = lgcn_detail::g_sample_blocks;
+    if (cap <= 0) {
+        int n_cu = 0;
+        if (const int rc = cu_count(&n_cu)) return rc;
+        cap = (int64_t)n_cu * kBlocksPerCu;
+    }
+    const int64_t want = (count + kBlock - 1) / kBlock;
+    *blocks = want < cap ? want : cap;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,19 +183,38 @@ int lgcn_bpr_sample(const int32_t* inter_user, const int32_t* inter_item, int64_
     if (!inter_user || !inter_item || !pos_rowptr || !pos_items) return LGCN_EINVAL;
     if (!users || !pos || !neg) return LGCN_EINVAL;
     if (count == 0) return 0;
-    int64_t blocks = (count + kBlock - 1) / kBlock;
-    int64_t cap = lgcn_detail::g_sample_blocks;
-    if (cap <= 0) {
-        int n_cu = 0;
-        if (const int rc = cu_count(&n_cu)) return rc;
-        cap = (int64_t)n_cu * kBlocksPerCu;
-    }
-    if (blocks > cap) blocks = cap;
+    int64_t blocks = 0;
+    if (const int rc = sample_blocks(count, &blocks)) return rc;
     hipLaunchKernelGGL(k_bpr_sample, dim3((uint32_t)blocks), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), inter_user, inter_item, n_inter,
                        order, first, count, pos_rowptr, pos_items, (int32_t)n_users,
                        (int32_t)n_items, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, users, pos,
                        neg, n_unsampled);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lgcn_bpr_sample_multi(const int32_t* inter_user, const int32_t* inter_item, int64_t n_inter,
+                          const int64_t* order, int64_t first, int64_t count,
+                          const int32_t* pos_rowptr, const int32_t* pos_items, int64_t n_users,
+                          int64_t n_items, uint64_t seed, uint32_t epoch, int32_t n_neg,
+                          int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_unsampled,
+                          void* stream) {
+    constexpr int64_t kLimit = (int64_t)1 << 31;
+    if (n_inter < 0 || n_users < 0 || n_items < 0) return LGCN_EINVAL;
+    if (n_inter >= kLimit || n_users >= kLimit || n_items >= kLimit) return LGCN_EINVAL;
+    if (first < 0 || count < 0 || first > INT64_MAX - count) return LGCN_EINVAL;
+    if (n_neg < 1 || n_neg > LGCN_BPR_MAX_NEG || count > INT64_MAX / n_neg) return LGCN_EINVAL;
+    if (count == 0) return 0;
+    if (!inter_user || !inter_item || !pos_rowptr || !pos_items) return LGCN_EINVAL;
+    if (!users || !pos || !neg) return LGCN_EINVAL;
+    int64_t blocks = 0;
+    if (const int rc = sample_blocks(count, &blocks)) return rc;
+    hipLaunchKernelGGL(k_bpr_sample_multi, dim3((uint32_t)blocks), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), inter_user, inter_item, n_inter,
+                       order, first, count, pos_rowptr, pos_items, (int32_t)n_users,
+                       (int32_t)n_items, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, n_neg,
+                       users, pos, neg, n_unsampled);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -45,6 +45,7 @@ TRACE_PHASES = ("start", "part0_blocks", "part1_blocks", "layer_kernel", "chain_
 ABI_VERSION = 14
 LGCN_EMU_CANDS, LGCN_EMU_META_BYTES, LGCN_EMU_BLOCK = 16, 16, 256
 ADAM_MAX_TENSORS, ADAM_CHUNK = 16, 4096  # LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK
+BPR_MAX_NEG = 64  # LGCN_BPR_MAX_NEG: negatives per sample (lgcn_bpr_sample_multi, _select_hardest)
 
 # Rows up to this degree run as row bundles in the layer kernel (one sequential fmaf chain each,
 # bitwise = reference CPU path). Longer rows ("hubs") follow the hub mode:
@@ -227,6 +228,11 @@ ABI = [
     ("lgcn_rows_clear", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),
     ("lgcn_bpr_sample", ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64,
                                        ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P, _P, _P]),
+    ("lgcn_bpr_sample_multi", ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64,
+                                             ctypes.c_uint64, ctypes.c_uint32, _I32, _P, _P, _P,
+                                             _P, _P]),
+    ("lgcn_bpr_select_hardest", ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _I32, _I32,
+                                               _I32, _P, _P, _P]),
     ("lgcn_fusion_prelayer", ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
     ("lgcn_fusion_prelayer_backward_scratch_bytes", ctypes.c_size_t, [_I32, _I32, _I32]),

@@ -20,6 +20,11 @@ positive (the reference never returns for one) gets neg = -1 and is counted in `
 bpr_step skips such a sample on a HIP device. Batch size, shuffle order, first / count windows and
 the launch geometry do not enter the draw; `epoch` and `seed` do.
 
+Several negatives per sample (`n_neg`, lgcn_bpr_sample_multi): ordinal m of an interaction is the
+same draw with the counter's last word set to m, so the ordinals are independent draws (repeats
+possible), column 0 is the one-negative draw and no column depends on n_neg. bpr_step trains on the
+hardest of them or on all (train.bpr_step, negatives=).
+
 Device dispatch, as the models and loss.py: a HIP `device` runs csrc/lgcn_sampler.hip (no
 fallback), a CPU `device` runs the same arithmetic as vectorised numpy — what a CPU-only user
 gets, and the reference the GPU tests compare the kernel against, bit for bit.
@@ -67,11 +72,13 @@ def mulhi64(r64, n):
     return (hi * n + ((lo * n) >> _S32)) >> _S32
 
 
-def random_j(idx, n_free, seed, epoch):
-    """j = mulhi64(r64(seed, epoch, idx), n_free) per element (int64)."""
+def random_j(idx, n_free, seed, epoch, ordinal=0):
+    """j = mulhi64(r64(seed, epoch, idx, ordinal), n_free) per element (int64); ordinal (a scalar
+    or an array that broadcasts against idx) is the counter's fourth word."""
     idx = np.asarray(idx, dtype=np.int64).astype(np.uint64)
     seed = int(seed)
-    o0, o1, _, _ = philox4x32_10(idx & _MASK32, idx >> _S32, np.uint64(int(epoch)), np.uint64(0),
+    o0, o1, _, _ = philox4x32_10(idx & _MASK32, idx >> _S32, np.uint64(int(epoch)),
+                                 np.asarray(ordinal, dtype=np.uint64),
                                  np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF))
     r64 = (o1.astype(np.uint64) << _S32) | o0.astype(np.uint64)
     return mulhi64(r64, n_free).astype(np.int64)
@@ -101,15 +108,31 @@ def kth_missing(pos_rowptr, pos_items, users, j):
 
 
 CHUNK = 1 << 16  # slots per piece of the numpy path: its temporaries stay in cache
+MAX_NEG = engine.BPR_MAX_NEG  # LGCN_BPR_MAX_NEG
+
+
+def check_n_neg(n_neg, what="sampler"):
+    """n_neg as every entry point here takes it: None (one negative, a 1-D `neg`) or an integer in
+    [1, MAX_NEG] (`neg` of shape [count, n_neg]); anything else raises ValueError."""
+    if n_neg is None:
+        return None
+    if isinstance(n_neg, bool) or not isinstance(n_neg, (int, np.integer)) or \
+            not 1 <= n_neg <= MAX_NEG:
+        raise ValueError(f"{what}: n_neg must be None or an integer in [1, {MAX_NEG}], "
+                         f"got {n_neg!r}")
+    return int(n_neg)
 
 
 def sample_numpy(inter_user, inter_item, order, first, count, pos_rowptr, pos_items, n_users,
-                 n_items, seed, epoch):
+                 n_items, seed, epoch, n_neg=None):
     """lgcn_bpr_sample's contract on the host, vectorised: (users, pos, neg) int64 arrays of
     `count` slots and the number of samples left without a negative. Slots whose interaction
     index or user lies outside its range are -1 in all three, as the kernel writes them. Runs in
     pieces of CHUNK slots on a few threads (numpy releases the GIL; a slot's result does not
-    depend on the split)."""
+    depend on the split). n_neg = an integer: lgcn_bpr_sample_multi's contract, neg of shape
+    [count, n_neg], column m drawn with counter word 3 = m (column 0 = the one-negative draw); a
+    slot without a free item counts once."""
+    n_neg = check_n_neg(n_neg, "sample_numpy")
     inter_user = np.asarray(inter_user)
     inter_item = np.asarray(inter_item)
     rowptr = np.asarray(pos_rowptr)
@@ -117,7 +140,8 @@ def sample_numpy(inter_user, inter_item, order, first, count, pos_rowptr, pos_it
     order = None if order is None else np.asarray(order, dtype=np.int64)
     users = np.full(count, -1, dtype=np.int64)
     pos = np.full(count, -1, dtype=np.int64)
-    neg = np.full(count, -1, dtype=np.int64)
+    neg = np.full(count if n_neg is None else (count, n_neg), -1, dtype=np.int64)
+    cols = neg.reshape(count, n_neg or 1)  # a view
 
     def piece(b):
         e = min(b + CHUNK, count)
@@ -133,8 +157,9 @@ def sample_numpy(inter_user, inter_item, order, first, count, pos_rowptr, pos_it
         pos[b:e][sel] = inter_item[idx]
         n_free = n_items - (rowptr[u + 1].astype(np.int64) - rowptr[u])
         free = n_free > 0
-        j = random_j(idx[free], n_free[free], seed, epoch)
-        neg[b:e][sel[free]] = kth_missing(rowptr, items, u[free], j)
+        for m in range(cols.shape[1]):
+            j = random_j(idx[free], n_free[free], seed, epoch, m)
+            cols[b:e, m][sel[free]] = kth_missing(rowptr, items, u[free], j)
         return int(free.size - free.sum())
 
     starts = range(0, count, CHUNK)
@@ -147,10 +172,12 @@ def sample_numpy(inter_user, inter_item, order, first, count, pos_rowptr, pos_it
 
 
 def sample_device(inter_user, inter_item, order, first, count, pos_rowptr, pos_items, n_users,
-                  n_items, seed, epoch, unsampled=None):
+                  n_items, seed, epoch, unsampled=None, n_neg=None):
     """lgcn_bpr_sample on the HIP device of `inter_user` (int32 tensors; order: int64 or None),
     on the caller's current stream: (users, pos, neg) int64 tensors of `count` slots. unsampled:
-    None, or the device int32 counter the kernel adds to (the caller zeroes it)."""
+    None, or the device int32 counter the kernel adds to (the caller zeroes it). n_neg = an
+    integer: lgcn_bpr_sample_multi, neg of shape [count, n_neg]; still one launch."""
+    n_neg = check_n_neg(n_neg, "sample_device")
     lib = engine.load_library()
     dev = inter_user.device
     for name, t, dt in (("inter_user", inter_user, torch.int32), ("inter_item", inter_item,
@@ -169,10 +196,21 @@ def sample_device(inter_user, inter_item, order, first, count, pos_rowptr, pos_i
         raise engine.LgcnError("sampler: pos_rowptr must hold num_users + 1 entries")
     if first < 0 or count < 0:
         raise engine.LgcnError("sampler: negative first or count")
+    P = engine._ptr
+    if n_neg is not None:
+        out = torch.empty((2, count), dtype=torch.int64, device=dev)
+        neg = torch.empty((count, n_neg), dtype=torch.int64, device=dev)
+        if count:
+            with torch.cuda.device(dev):
+                engine._check(lib.lgcn_bpr_sample_multi(
+                    P(inter_user), P(inter_item), inter_user.numel(), P(order), first, count,
+                    P(pos_rowptr), P(pos_items), n_users, n_items, ctypes.c_uint64(int(seed)),
+                    ctypes.c_uint32(int(epoch)), n_neg, P(out[0]), P(out[1]), P(neg),
+                    P(unsampled), engine._stream(dev)), "lgcn_bpr_sample_multi")
+        return out[0], out[1], neg
     out = torch.empty((3, count), dtype=torch.int64, device=dev)
     if count == 0:  # nothing to launch (and an empty tensor has no pointer to pass)
         return out[0], out[1], out[2]
-    P = engine._ptr
     with torch.cuda.device(dev):
         engine._check(lib.lgcn_bpr_sample(
             P(inter_user), P(inter_item), inter_user.numel(), P(order), first, count,
@@ -230,11 +268,20 @@ class BprSampler:
     def __len__(self):
         return self._n
 
-    def draw(self, epoch, order=None, first=0, count=None):
+    def draw(self, epoch, order=None, first=0, count=None, n_neg=None):
         """(users, pos, neg): int64 tensors on the sampler's device for output slots [0, count):
         slot s is interaction order[first + s] (order: an int64 index tensor on the device, e.g. a
         permutation; None = identity). count=None: up to the end of the order. One launch on the
-        current stream, no host read-back; `unsampled` is reset and counts this draw."""
+        current stream, no host read-back; `unsampled` is reset and counts this draw.
+
+        n_neg=None: one negative per sample, `neg` 1-D (lgcn_bpr_sample). n_neg = an integer in
+        [1, 64]: `neg` of shape [count, n_neg] (lgcn_bpr_sample_multi), column m the draw with
+        counter word 3 = m — independent draws over the user's complement (the same item may come
+        up twice), column 0 the one-negative draw, no column depending on n_neg; `unsampled` still
+        counts slots. Anything else raises ValueError. The draw holds count * (2 + n_neg) * 8
+        bytes (a whole C3 epoch of 29.5M samples at n_neg = 16: 4.2 GB); it is one launch
+        whatever n_neg."""
+        n_neg = check_n_neg(n_neg, "BprSampler.draw")
         epoch = int(epoch)
         if not 0 <= epoch < 1 << 32:
             raise ValueError("BprSampler.draw: epoch must fit 32 unsigned bits")
@@ -253,12 +300,12 @@ class BprSampler:
             return sample_device(self._user, self._item,
                                  None if order is None else order.contiguous(), first, count,
                                  self._rowptr, self._pos_items, self.num_users, self.num_items,
-                                 self.seed, epoch, self.unsampled)
+                                 self.seed, epoch, self.unsampled, n_neg)
         if torch.is_tensor(order):
             order = order.numpy()
         u, p, n, missed = sample_numpy(self._user, self._item, order, first, count, self._rowptr,
                                        self._pos_items, self.num_users, self.num_items, self.seed,
-                                       epoch)
+                                       epoch, n_neg)
         self.unsampled.fill_(missed)
         return torch.from_numpy(u), torch.from_numpy(p), torch.from_numpy(n)
 
@@ -271,14 +318,19 @@ class BprSampler:
         g.manual_seed((self.seed + SHUFFLE_MIX * int(epoch)) % (1 << 63))
         return torch.randperm(self._n, generator=g, device=self.device)
 
-    def epoch(self, epoch, batch_size, shuffle=True, drop_last=False):
+    def epoch(self, epoch, batch_size, shuffle=True, drop_last=False, n_neg=None):
         """One draw for the whole epoch (one launch), made by this call (so `unsampled` counts it
         on return), then an iterator of (users, pos, neg) views of it batch by batch: no launch,
-        copy or sync per batch. The last batch is short unless drop_last."""
+        copy or sync per batch. The last batch is short unless drop_last. n_neg is draw()'s: with
+        an integer a batch's `neg` is the [batch, n_neg] row view of the draw (contiguous), what
+        bpr_step takes for negatives="hardest" / "all"; the draw then holds
+        len(self) * (2 + n_neg) * 8 bytes."""
+        n_neg = check_n_neg(n_neg, "BprSampler.epoch")
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("BprSampler.epoch: batch_size must be positive")
-        users, pos, neg = self.draw(epoch, self.permutation(epoch) if shuffle else None)
+        users, pos, neg = self.draw(epoch, self.permutation(epoch) if shuffle else None,
+                                    n_neg=n_neg)
         end = self._n - self._n % batch_size if drop_last else self._n
 
         def views():

@@ -25,6 +25,12 @@ block through the device-resident map (lgcn_bpr_brand_loss_indexed), the batch 5
 (lgcn_bpr_brand_keys) and the STORE scatter covers the brand rows of the workspace. Bitwise the
 gathered route through loss.bpr_brand_loss_reg.
 
+With a [B, M] `neg` (several candidate negatives per sample, sampler.BprSampler.epoch(n_neg=M))
+the step trains on the hardest candidate — dynamic negative sampling — at the cost of one small
+kernel: lgcn_bpr_select_hardest runs between the propagation and the loss, on the tables the loss
+is about to read, and scores a candidate by the loss kernel's own expression. The route composed
+of public calls (model(adj) under no_grad, gather, argmax, bpr_step) propagates twice.
+
 `bpr_epoch` is the loop around it (main.py:488-531): the batches are views of one device-side draw
 of sampler.BprSampler, the per-batch losses come back as one device tensor.
 """
@@ -105,8 +111,90 @@ def _scatter(lib, ws, m, src, lo, hi, dst, mode, mask, count, stream):
                                         engine._ptr(count), stream), "lgcn_rows_scatter")
 
 
+def _check_candidates(cand, device, B=None):
+    """A 2-D `neg`: int64 [B, M], contiguous, on `device`, 1 <= M <= engine.BPR_MAX_NEG."""
+    if not torch.is_tensor(cand) or cand.dtype != torch.int64:
+        raise engine.LgcnError("bpr_step: neg must be an int64 tensor "
+                               f"(got {getattr(cand, 'dtype', type(cand))})")
+    if cand.dim() != 2 or not cand.is_contiguous():
+        raise engine.LgcnError("bpr_step: several negatives per sample are a contiguous "
+                               f"[B, M] tensor, got shape {tuple(cand.shape)} strides "
+                               f"{cand.stride()}")
+    if cand.device != device:
+        raise engine.LgcnError(f"bpr_step: neg on {cand.device}, adjacency on {device}")
+    if not 1 <= int(cand.shape[1]) <= engine.BPR_MAX_NEG:
+        raise engine.LgcnError(f"bpr_step: {int(cand.shape[1])} negatives per sample "
+                               f"(1 to {engine.BPR_MAX_NEG})")
+    if B is not None and int(cand.shape[0]) != B:
+        raise engine.LgcnError("bpr_step: users, pos and neg must have one length")
+
+
+def select_hardest(fu, fi, users, cand, return_scores=False):
+    """lgcn_bpr_select_hardest on the HIP device of `fu`, on the caller's current stream: per
+    sample the candidate of cand[b] (int64 [B, M], 1 <= M <= 64) that the final tables fu / fi
+    ([rows x d] fp32, unit column stride; row slices of one buffer are fine) score highest for
+    users[b], int64 [B]. The first candidate in range is the choice until a later one in range
+    scores greater (>): ties go to the lower ordinal, a candidate outside [0, items) (the
+    sampler's -1) is passed over, and a sample with no candidate in range or a user out of range
+    gets -1. return_scores=True: (negatives, scores), scores[b] bitwise the negative score the
+    loss kernel forms for negatives[b] (NaN where the negative is -1)."""
+    dev = fu.device
+    if dev.type != "cuda":
+        raise engine.LgcnError("select_hardest: the tables must be on a HIP device")
+    for name, t in (("fu", fu), ("fi", fi)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.device != dev or \
+                (t.numel() and t.stride(1) != 1):
+            raise engine.LgcnError(f"select_hardest: {name} must be a [rows x d] fp32 table on "
+                                   f"{dev} with unit column stride")
+    d = int(fu.shape[1])
+    if int(fi.shape[1]) != d or d < 1:
+        raise engine.LgcnError("select_hardest: fu and fi must have one width d >= 1")
+    if not torch.is_tensor(users) or users.dtype != torch.int64 or users.dim() != 1 or \
+            users.device != dev or not users.is_contiguous():
+        raise engine.LgcnError(f"select_hardest: users must be a contiguous 1-D int64 tensor on "
+                               f"{dev}")
+    B = int(users.shape[0])
+    _check_candidates(cand, dev, B)
+    lib = engine.load_library()
+    neg = torch.empty(B, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, dtype=torch.float32, device=dev) if return_scores else None
+    if B:
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_bpr_select_hardest(
+                engine._ptr(fu), fu.stride(0) if fu.shape[0] else d, engine._ptr(fi),
+                fi.stride(0) if fi.shape[0] else d, int(fu.shape[0]), int(fi.shape[0]),
+                engine._ptr(users), engine._ptr(cand), B, int(cand.shape[1]), d,
+                engine._ptr(neg), engine._ptr(scores), engine._stream(dev)),
+                "lgcn_bpr_select_hardest")
+    return (neg, scores) if return_scores else neg
+
+
+def select_hardest_torch(fu, fi, users, cand):
+    """select_hardest's rule in torch ops (what a CPU adjacency runs): (negatives, found), found[b]
+    False where no candidate of sample b lies in range or its user does not. Scores are torch's
+    own sums, so against the HIP kernel two candidates whose scores differ in the last bits may
+    swap: the rule is the same, the bits of a score are not claimed across devices."""
+    U, I = int(fu.shape[0]), int(fi.shape[0])
+    valid = ((cand >= 0) & (cand < I)) & ((users >= 0) & (users < U)).unsqueeze(1)
+    with torch.no_grad():
+        rows = fi[cand.clamp(0, max(I - 1, 0))]                       # [B, M, d]
+        scores = (fu[users.clamp(0, max(U - 1, 0))].unsqueeze(1) * rows).sum(-1)
+    best = torch.full_like(users, -1)
+    best_s = torch.zeros(users.shape, dtype=scores.dtype, device=scores.device)
+    for m in range(int(cand.shape[1])):  # ascending ordinal: replace only on a greater score
+        take = valid[:, m] & ((best < 0) | (scores[:, m] > best_s))
+        best = torch.where(take, cand[:, m], best)
+        best_s = torch.where(take, scores[:, m], best_s)
+    return best, valid.any(1)
+
+
 class BprStepFunction(torch.autograd.Function):
     """(graph, K, hub_threshold, lambda_reg, users, pos, neg, n_e0, *segments) -> the loss.
+
+    neg [B]: the step on those negatives. neg [B, M] (several candidates per sample): after the
+    propagation, lgcn_bpr_select_hardest picks each sample's negative from this step's final
+    tables, the ones the loss is about to read; loss, keys and scatter run on the picked [B]
+    negatives, which are saved for backward in place of neg, and (loss, negatives) is returned.
 
     Mirrors engine.PropagateFunction: segments = the (user, item, brand) layer-0 blocks the
     propagation reads; the first n_e0 of them are also the tables the regulariser's rows come
@@ -135,6 +223,9 @@ class BprStepFunction(torch.autograd.Function):
             raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
         B = int(users.shape[0])
         fu, fi, u0 = out[:U], out[U:U + I], segs[0]
+        picked = neg.dim() == 2
+        if picked:
+            neg = select_hardest(fu, fi, users, neg)
         terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grads = torch.empty((6, B, d), dtype=torch.float32, device=dev)
@@ -147,10 +238,13 @@ class BprStepFunction(torch.autograd.Function):
         ctx.save_for_backward(grads, users, pos, neg)
         ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
         ctx.sizes, ctx.n_e0, ctx.n_inputs = sizes, n_e0, len(segments)
+        if picked:
+            ctx.mark_non_differentiable(neg)
+            return loss, neg
         return loss
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         grads, users, pos, neg = ctx.saved_tensors
         graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
         U, I = sizes[0], sizes[1]
@@ -225,6 +319,9 @@ class BprBrandStepFunction(torch.autograd.Function):
             raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
         B = int(users.shape[0])
         fu, fi, fb, u0 = out[:U], out[U:U + I], out[U + I:U + I + NB], segs[0]
+        picked = neg.dim() == 2
+        if picked:  # the brand rows then follow the picked item
+            neg = select_hardest(fu, fi, users, neg)
         terms = torch.empty(3 * B, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grads = torch.empty((8, B, d), dtype=torch.float32, device=dev)
@@ -239,10 +336,13 @@ class BprBrandStepFunction(torch.autograd.Function):
         ctx.save_for_backward(grads, users, pos, neg, item_brand)
         ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
         ctx.sizes, ctx.n_e0 = sizes, n_e0
+        if picked:
+            ctx.mark_non_differentiable(neg)
+            return loss, neg
         return loss
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         grads, users, pos, neg, item_brand = ctx.saved_tensors
         graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
         U, I, NB = sizes
@@ -307,7 +407,8 @@ def _check_item_brand(item_brand, num_items, device):
 
 def _check_index_tensors(users, pos, neg, device):
     B = None
-    for name, t in (("users", users), ("pos", pos), ("neg", neg)):
+    many = torch.is_tensor(neg) and neg.dim() != 1  # [B, M]: several negatives per sample
+    for name, t in (("users", users), ("pos", pos)) + ((() if many else (("neg", neg),))):
         if not torch.is_tensor(t) or t.dtype != torch.int64:
             raise engine.LgcnError(f"bpr_step: {name} must be an int64 tensor "
                                    f"(got {getattr(t, 'dtype', type(t))})")
@@ -319,12 +420,30 @@ def _check_index_tensors(users, pos, neg, device):
             B = int(t.shape[0])
         elif int(t.shape[0]) != B:
             raise engine.LgcnError("bpr_step: users, pos and neg must have one length")
+    if many:
+        _check_candidates(neg, device, B)
     if B < 1:
         raise engine.LgcnError("bpr_step: empty batch")
 
 
+def _cpu_loss(tables, users, pos, neg, lambda_reg, item_brand, brand_loss_weight):
+    """The reference's own expression on model(adj)'s five tables (the CPU route)."""
+    fu, fi, fb, u0, i0 = tables
+    if item_brand is None:
+        return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg],
+                            lambda_reg, final_brand_emb=fb)
+    pb, nb = item_brand[pos].long(), item_brand[neg].long()
+    n_brands = int(fb.shape[0])
+    if bool(((pb < 0) | (pb >= n_brands) | (nb < 0) | (nb >= n_brands)).any()):
+        raise engine.LgcnError("bpr_step: an item of the batch has no brand; the CPU route "
+                               "cannot leave the sample out of the brand term")
+    return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg], lambda_reg,
+                        brand_loss=True, final_brand_emb=fb, pos_item_brand_idx=pb,
+                        neg_item_brand_idx=nb, brand_loss_weight=brand_loss_weight)
+
+
 def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, item_brand=None,
-             brand_loss_weight=0.1):
+             brand_loss_weight=0.1, negatives="hardest", return_negatives=False):
     """The loss of one BPR batch (main.py:495-522) as a tensor whose
     `.backward()` leaves exactly the parameter `.grad`s main.py's route leaves:
 
@@ -347,29 +466,57 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
     positive or negative item has no brand contributes no brand term (the mean still divides by
     the batch size). item_brand=None or brand_loss_weight == 0 is the step without the term. On a
     CPU adjacency bpr_loss_reg(brand_loss=True, ...) runs; an unbranded item in the batch raises
-    LgcnError there, where the reference's indexing would take -1 for the last brand."""
+    LgcnError there, where the reference's indexing would take -1 for the last brand.
+
+    Several negatives per sample: neg of shape [B, M] (int64, contiguous, on the adjacency's
+    device, 1 <= M <= 64, e.g. a batch of sampler.epoch(..., n_neg=M); anything else raises
+    LgcnError before any launch). A 1-D neg is the step above and `negatives` is not looked at.
+      negatives="hardest"  dynamic negative sampling: each sample trains on the candidate this
+          step's model scores highest. The choice is made inside the step, between its one
+          propagation and the loss (lgcn_bpr_select_hardest on the final tables the loss then
+          reads; select_hardest states the rule: first maximum, lowest ordinal, candidates
+          outside [0, items) passed over, a sample without one skipped). Loss and `.grad`s are
+          bitwise those of bpr_step(adj, users, pos, chosen); with item_brand the brand rows
+          follow the chosen item.
+      negatives="all"  BPR over the B*M pairs: by definition the step on
+          users.repeat_interleave(M), pos.repeat_interleave(M), neg.reshape(-1) — main.py's
+          formula on the expanded triples (its means divide by B*M).
+    Any other value raises ValueError. return_negatives=True returns (loss, neg_used), the int64
+    negatives the loss ran on: [B] for "hardest" (and for a 1-D neg, neg itself), [B*M] for "all".
+    check_indices=True validates every entry of a 2-D neg. On a CPU adjacency model(adj) runs
+    once, the candidates are scored and chosen with torch ops by the same rule
+    (select_hardest_torch) and the reference expression runs on the choice; a sample without a
+    candidate in range raises LgcnError (the reference's indexing would take -1 for the last
+    item; bpr_epoch refuses a neg = -1 there for the same reason). The choice is not claimed
+    bitwise across devices: torch sums a score in another order, so two candidates whose scores
+    differ in the last bits can swap."""
     _check_index_tensors(users, pos, neg, adj.device)
     U, I = model.num_users, model.num_items
     brand = item_brand is not None and brand_loss_weight != 0
     if brand:
         _check_item_brand(item_brand, I, adj.device)
+    many = neg.dim() == 2
+    if many and negatives not in ("hardest", "all"):
+        raise ValueError(f"bpr_step: negatives={negatives!r} ('hardest' or 'all')")
     if check_indices:
         for name, t, n in (("users", users, U), ("pos", pos, I), ("neg", neg, I)):
             if bool(((t < 0) | (t >= n)).any()):
                 raise engine.LgcnError(f"bpr_step: {name} holds an index outside [0, {n})")
+    if many and negatives == "all":
+        M = int(neg.shape[1])
+        return bpr_step(model, adj, users.repeat_interleave(M), pos.repeat_interleave(M),
+                        neg.reshape(-1), lambda_reg, item_brand=item_brand,
+                        brand_loss_weight=brand_loss_weight, return_negatives=return_negatives)
     if adj.device.type != "cuda":
-        fu, fi, fb, u0, i0 = model(adj)
-        if not brand:
-            return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg],
-                                lambda_reg, final_brand_emb=fb)
-        pb, nb = item_brand[pos].long(), item_brand[neg].long()
-        n_brands = int(fb.shape[0])
-        if bool(((pb < 0) | (pb >= n_brands) | (nb < 0) | (nb >= n_brands)).any()):
-            raise engine.LgcnError("bpr_step: an item of the batch has no brand; the CPU route "
-                                   "cannot leave the sample out of the brand term")
-        return bpr_loss_reg(fu[users], fi[pos], fi[neg], u0[users], i0[pos], i0[neg], lambda_reg,
-                            brand_loss=True, final_brand_emb=fb, pos_item_brand_idx=pb,
-                            neg_item_brand_idx=nb, brand_loss_weight=brand_loss_weight)
+        tables = model(adj)
+        if many:
+            neg, found = select_hardest_torch(tables[0], tables[1], users, neg)
+            if not bool(found.all()):
+                raise engine.LgcnError("bpr_step: a sample has no candidate negative in range; "
+                                       "the CPU route cannot skip the sample")
+        loss = _cpu_loss(tables, users, pos, neg, lambda_reg, item_brand if brand else None,
+                         brand_loss_weight)
+        return (loss, neg) if return_negatives else loss
     n_e0 = model._bpr_n_e0
     if n_e0 == 2:
         tensors = [model.user_embedding.weight, model.item_embedding.weight,
@@ -379,15 +526,18 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
                    model.brand_embedding.weight, model.item_id_embedding.weight]
     graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
     if brand:
-        return BprBrandStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
-                                          float(lambda_reg), float(brand_loss_weight), users, pos,
-                                          neg, item_brand, n_e0, *tensors)
-    return BprStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
-                                 float(lambda_reg), users, pos, neg, n_e0, *tensors)
+        out = BprBrandStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                         float(lambda_reg), float(brand_loss_weight), users, pos,
+                                         neg, item_brand, n_e0, *tensors)
+    else:
+        out = BprStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                    float(lambda_reg), users, pos, neg, n_e0, *tensors)
+    loss, used = out if many else (out, neg)  # a 2-D neg: (loss, the chosen negatives)
+    return (loss, used) if return_negatives else loss
 
 
 def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
-              item_brand=None, brand_loss_weight=0.1):
+              item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest"):
     """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
     epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
     batch
@@ -402,18 +552,26 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     take -1 for the last item, it raises before the first optimizer step. item_brand and
     brand_loss_weight are bpr_step's: the brand loss of every batch, looked up on the device.
     Any optimizer works; `optim.Adam(model.parameters(), lr)` keeps the whole step inside the
-    engine (one launch, lgcn_adam_step) and leaves torch.optim.Adam's bits."""
+    engine (one launch, lgcn_adam_step) and leaves torch.optim.Adam's bits.
+
+    n_neg (None = the epoch above; an integer in [1, 64]) is passed to sampler.epoch: the draw
+    holds n_neg candidate negatives per sample and every batch's neg is [batch, n_neg]; negatives
+    ("hardest" or "all") is bpr_step's and says what the step does with them."""
     if sampler.device != adj.device:
         raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
-    batches = sampler.epoch(epoch, batch_size, shuffle=shuffle)  # the draw is made here
+    if n_neg is not None and negatives not in ("hardest", "all"):
+        raise ValueError(f"bpr_epoch: negatives={negatives!r} ('hardest' or 'all')")
+    # the draw is made here
+    batches = sampler.epoch(epoch, batch_size, shuffle=shuffle, n_neg=n_neg)
     if adj.device.type != "cuda" and int(sampler.unsampled.item()):
         raise engine.LgcnError("bpr_epoch: a user has every item as a positive (no negative to "
                                "draw); the CPU route cannot skip the sample")
+    many = {} if n_neg is None else {"negatives": negatives}
     losses = []
     for users, pos, neg in batches:
         optimizer.zero_grad()
         loss = model.bpr_step(adj, users, pos, neg, lambda_reg, item_brand=item_brand,
-                              brand_loss_weight=brand_loss_weight)
+                              brand_loss_weight=brand_loss_weight, **many)
         loss.backward()
         optimizer.step()
         losses.append(loss.detach())

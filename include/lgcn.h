@@ -61,8 +61,10 @@ extern "C" {
  * backward (lgcn_fusion_prelayer_backward, its scratch query, LGCN_FUSION_BWD_CHUNK,
  * LGCN_TUNE_FUSION_BWD_BLOCKS) and the Adam step (lgcn_adam_step, lgcn_adam_chunks, their two
  * structs, LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK) and the wide recommendation lists
- * (lgcn_score_topk_wide, lgcn_topk_wide_splits, its scratch query, LGCN_TOPK_WIDE_MAX_K) were
- * added without a bump: purely additive, no existing symbol, struct or constant changed. */
+ * (lgcn_score_topk_wide, lgcn_topk_wide_splits, its scratch query, LGCN_TOPK_WIDE_MAX_K) and
+ * several negatives per sample (lgcn_bpr_sample_multi, lgcn_bpr_select_hardest,
+ * LGCN_BPR_MAX_NEG) were added without a bump: purely additive, no existing symbol, struct or
+ * constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -836,6 +838,51 @@ int lgcn_bpr_sample(const int32_t* inter_user, const int32_t* inter_item, int64_
                     const int32_t* pos_rowptr, const int32_t* pos_items, int64_t n_users,
                     int64_t n_items, uint64_t seed, uint32_t epoch, int64_t* users, int64_t* pos,
                     int64_t* neg, int32_t* n_unsampled, void* stream);
+
+/* lgcn_bpr_sample with n_neg negatives per sample, neg = int64 [count x n_neg] row-major (a
+ * slot's n_neg entries side by side). Entry m ("ordinal m") of interaction idx is the draw above
+ * with the counter's fourth word set to m: Philox counter (idx_lo32, idx_hi32, epoch, m); key,
+ * r64, range reduction and selection unchanged. So column 0 is lgcn_bpr_sample's negative bit for
+ * bit, and column m depends neither on n_neg nor on anything the draw above does not depend on.
+ * The ordinals of a slot are independent draws over the complement of the user's list: the same
+ * item may come up more than once (no sequential exclusion, which would tie column m to the
+ * columns before it). A slot whose interaction or user is out of range has -1 in users, pos and
+ * all n_neg entries; a user without a free item -1 in all n_neg entries, and *n_unsampled rises
+ * once for the slot. Refused on the host (LGCN_EINVAL), in this order: the sizes lgcn_bpr_sample
+ * refuses; n_neg outside [1, LGCN_BPR_MAX_NEG]; count * n_neg past int64. Then count == 0 returns
+ * 0, launches nothing and looks at no pointer; then a NULL pointer other than order /
+ * n_unsampled / stream (LGCN_EINVAL). */
+#define LGCN_BPR_MAX_NEG 64
+int lgcn_bpr_sample_multi(const int32_t* inter_user, const int32_t* inter_item, int64_t n_inter,
+                          const int64_t* order, int64_t first, int64_t count,
+                          const int32_t* pos_rowptr, const int32_t* pos_items, int64_t n_users,
+                          int64_t n_items, uint64_t seed, uint32_t epoch, int32_t n_neg,
+                          int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_unsampled,
+                          void* stream);
+
+/* Dynamic negative sampling: per sample the hardest of n_neg candidate negatives, neg_out[b] =
+ * the candidate the current tables score highest for users[b] (cand: device int64 [B x n_neg]
+ * row-major, e.g. lgcn_bpr_sample_multi's neg; fu / fi: the final user / item tables).
+ *  - Score of candidate m: <fu[users[b]], fi[cand[b][m]]> by the expression lgcn_bpr_loss_indexed
+ *    forms its negative score with (one device function, called by both): per lane an fmaf chain
+ *    over k = lane, lane + 64, ... from +0, then the 32, 16, ..., 1 xor butterfly. score_out[b]
+ *    (NULL = not wanted) is therefore bitwise the negative score the loss kernel forms for
+ *    neg_out[b]; it does not depend on how many candidate rows the kernel loads at a time.
+ *  - Rule (NaN scores included): the choice starts as the first candidate, in ascending m, whose
+ *    index lies in [0, n_items); a later candidate in range replaces it only if its score compares
+ *    greater (>). A tie between different items goes to the lower ordinal; a NaN score is kept if
+ *    it comes first and never chosen later.
+ *  - Memory safety: a candidate outside [0, n_items) (the sampler's -1) is passed over and nothing
+ *    of it is dereferenced. A sample whose user lies outside [0, n_users) or which has no
+ *    candidate in range gets neg_out = -1 and score_out = NaN, and a training step skips it.
+ * Any d >= 1 and ld >= d. Allocates nothing, never synchronises, everything runs on `stream`.
+ * LGCN_EINVAL before any launch: B < 0, d < 1, n_neg outside [1, LGCN_BPR_MAX_NEG], ld < d,
+ * n_users or n_items < 0; then B == 0 returns 0 and looks at no pointer; then a NULL pointer
+ * other than score_out / stream (LGCN_EINVAL). */
+int lgcn_bpr_select_hardest(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                            int64_t n_users, int64_t n_items, const int64_t* users,
+                            const int64_t* cand, int32_t B, int32_t n_neg, int32_t d,
+                            int64_t* neg_out, float* score_out, void* stream);
 
 /* ---- LightGCN_Fusion item pre-layer (models/lightgcn_fusion.py:45-49) ------------------------ */
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,

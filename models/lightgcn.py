@@ -113,22 +113,27 @@ class LightGCN(nn.Module):
     _bpr_n_e0 = 2  # the regulariser's user and item rows come from the propagation's segments
 
     def bpr_step(self, adj, users, pos, neg, lambda_reg, *, item_brand=None,
-                 brand_loss_weight=0.1):
+                 brand_loss_weight=0.1, negatives="hardest", return_negatives=False):
         """The BPR + L2 loss of one batch (main.py:495-522) in one call that keeps the batch
         indices: `.backward()` leaves the `.grad`s of the hand-written route, to the bit
-        (train.bpr_step). item_brand (data.item_brand_map) adds the brand loss."""
+        (train.bpr_step). item_brand (data.item_brand_map) adds the brand loss. A [B, M] neg
+        holds M candidate negatives per sample: negatives="hardest" trains on the one the model
+        scores highest, chosen inside the step; "all" on every pair."""
         return train.bpr_step(self, adj, users, pos, neg, lambda_reg, item_brand=item_brand,
-                              brand_loss_weight=brand_loss_weight)
+                              brand_loss_weight=brand_loss_weight, negatives=negatives,
+                              return_negatives=return_negatives)
 
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
-                  item_brand=None, brand_loss_weight=0.1):
+                  item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest"):
         """One epoch of bpr_step batches over one device-side draw of the sampler
         (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
         `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
-        engine, with torch.optim.Adam's bits."""
+        engine, with torch.optim.Adam's bits. n_neg = M draws M candidate negatives per sample
+        for bpr_step's `negatives` mode."""
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
-                               brand_loss_weight=brand_loss_weight)
+                               brand_loss_weight=brand_loss_weight, n_neg=n_neg,
+                               negatives=negatives)
 
     def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
         """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass

@@ -19,9 +19,15 @@ the plain bpr_step beside them. bpr_step_brand's first batch is asserted bit-equ
 route through loss.bpr_brand_loss_reg; against bpr_loss_reg's torch expression of the brand term
 the relative loss difference is reported.
 
+--negatives M times training on the hardest of M candidate negatives instead (and nothing else):
+the plain one-negative step, the fused bpr_step(neg [B, M], negatives="hardest") and the route
+composed of the one-negative API (model(adj) under no_grad, gather, argmax, bpr_step), forward +
+backward, in alternating blocks of one process (time_negatives).
+
 Prints one JSON line on stdout (progress goes to stderr).
 
     python tools/bpr_step_bench.py [--config c3] [--blocks 5] [--steps-per-block 4] [--brand-loss]
+    python tools/bpr_step_bench.py --negatives 4
 """
 import argparse
 import contextlib
@@ -80,8 +86,85 @@ def bits_equal(a, b):
                                               b.detach().view(torch.int32))
 
 
+def time_negatives(args, M, adj, m, U, I, dev, result):
+    """--negatives M: three routes in alternating blocks of whole forward + backward steps (no
+    optimizer: the one model stays put, so every route sees the same tables on every batch),
+      plain     the one-negative bpr_step on candidate 0;
+      fused     bpr_step on the [B, M] candidates, negatives="hardest": one propagation, the
+                choice made between it and the loss;
+      composed  what the one-negative API alone allows: model(adj) under no_grad, gather, argmax,
+                then bpr_step on the choice — two propagations.
+    The first batch's fused and composed choices are compared (torch's score sums may break a
+    near-tie the other way: the count of differing samples is reported, not asserted)."""
+    rng = np.random.default_rng(1)
+    n_batches = args.blocks * args.steps_per_block + args.warmup
+    batches = [(torch.from_numpy(rng.integers(0, U, args.batch)).to(dev),
+                torch.from_numpy(rng.integers(0, I, args.batch)).to(dev),
+                torch.from_numpy(rng.integers(0, I, (args.batch, M))).to(dev))
+               for _ in range(n_batches)]
+
+    def plain(m, users, pos, cand):
+        return m.bpr_step(adj, users, pos, cand[:, 0].contiguous(), LAMBDA)
+
+    def fused(m, users, pos, cand):
+        return m.bpr_step(adj, users, pos, cand, LAMBDA, negatives="hardest")
+
+    def composed_choice(m, users, cand):
+        with torch.no_grad():
+            fu, fi = m(adj, use_brand=False)[:2]
+            scores = (fu[users].unsqueeze(1) * fi[cand]).sum(-1)
+            return cand.gather(1, scores.argmax(1, keepdim=True)).squeeze(1)
+
+    def composed(m, users, pos, cand):
+        return m.bpr_step(adj, users, pos, composed_choice(m, users, cand), LAMBDA)
+
+    routes = (("plain", plain), ("fused_hardest", fused), ("composed_hardest", composed))
+    users, pos, cand = batches[-1]
+    _, used = m.bpr_step(adj, users, pos, cand, LAMBDA, return_negatives=True)
+    differ = int((used != composed_choice(m, users, cand)).sum().item())
+
+    def step(fn, b):
+        m.zero_grad(set_to_none=True)
+        fn(m, *b).backward()
+
+    for name, fn in routes:
+        for b in batches[:args.warmup]:
+            step(fn, b)
+    per_block = {name: [] for name, _ in routes}
+    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for blk in range(args.blocks):
+        lo = args.warmup + blk * args.steps_per_block
+        for name, fn in routes:
+            torch.cuda.synchronize()
+            a.record()
+            for b in batches[lo:lo + args.steps_per_block]:
+                step(fn, b)
+            e.record()
+            torch.cuda.synchronize()
+            per_block[name].append(a.elapsed_time(e) / args.steps_per_block)
+    med = {name: float(np.median(v)) for name, v in per_block.items()}
+    result.update(
+        negatives=M,
+        step_ms={name: round(v, 3) for name, v in med.items()},
+        step_block_ms={name: [round(x, 3) for x in v] for name, v in per_block.items()},
+        spread_ms={name: round(float(np.ptp(v)), 3) for name, v in per_block.items()},
+        fused_minus_plain_ms=round(med["fused_hardest"] - med["plain"], 3),
+        composed_minus_fused_ms=round(med["composed_hardest"] - med["fused_hardest"], 3),
+        fused_not_slower_than_composed=bool(med["fused_hardest"] <= med["composed_hardest"]),
+        first_batch_choices_differing=differ,
+        what=("forward + backward of one batch, zero_grad before, no optimizer step; events "
+              "around alternating blocks of steps per route, median over the blocks; spread_ms = "
+              "max - min of a route's block medians; plain = bpr_step on candidate 0, "
+              "fused_hardest = bpr_step(neg [B, M], negatives='hardest'), composed_hardest = "
+              "model(adj) under no_grad + gather + argmax + bpr_step"))
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--negatives", type=int, nargs="+", default=None, metavar="M",
+                    help="time the hardest-of-M step against the plain step and the composed "
+                         "route (and nothing else); several M: one after the other on one graph")
     ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
     ap.add_argument("--gen", default="powerlaw", choices=["powerlaw", "uniform"])
     ap.add_argument("--batch", type=int, default=2048)
@@ -110,6 +193,16 @@ def main():
                                   (n, n)).to(dev)
     nnz = len(v)
     del r, c, v
+    if args.negatives:
+        if args.brand_loss or not all(1 <= M <= engine.BPR_MAX_NEG for M in args.negatives):
+            sys.exit(f"bpr_step_bench: --negatives takes 1..{engine.BPR_MAX_NEG}, without "
+                     "--brand-loss")
+        model = make_model(emb_host, U, I, d, K, dev)
+        for M in args.negatives:   # one JSON line per M
+            result = {"config": cfg["name"], "nnz": nnz, "d": d, "K": K, "batch": args.batch,
+                      "blocks": args.blocks, "steps_per_block": args.steps_per_block}
+            time_negatives(args, M, adj, model, U, I, dev, result)
+        return
     if args.brand_loss:
         if NB < 1:
             sys.exit("bpr_step_bench: --brand-loss needs --brands >= 1")

@@ -17,6 +17,10 @@ against one training step of the commit before the sampler (profiles/bpr_step_c3
 
     timeout -k 10 840 python tools/sampler_bench.py [--config c3] [--reps 7] [--subset 200000]
 
+--n-neg M [M ...] times only the device draw with M negatives per sample (lgcn_bpr_sample_multi,
+shuffled order) beside the one-negative draw, the variants interleaved rep by rep, and compares
+the first slots of each with the numpy path.
+
 One process, so the three figures come from one machine in one run; it holds the GPU for the
 whole of it and is therefore started under a time limit of its own, as every GPU step is.
 """
@@ -72,6 +76,41 @@ def python_loop(users, items, rowptr, pos_items, n_items, subset):
     return (time.perf_counter() - t0) / max(len(sub_u), 1)
 
 
+def multi_neg(args, s, users, items, U, I, E, epoch, cfg):
+    """--n-neg: the whole-epoch shuffled device draw at each M (lgcn_bpr_sample_multi) and with
+    one negative (lgcn_bpr_sample), the variants interleaved rep by rep; the first --check slots
+    of every M are compared with the numpy path."""
+    perm = s.permutation(epoch)
+    variants = [None] + list(args.n_neg)
+    check = min(args.check, E, 100_000)
+    order = perm[:check].cpu().numpy()
+    c = sampler.BprSampler(users, items, U, I, "cpu", seed=args.seed)
+    for M in variants:   # warm-up and the comparison
+        got = s.draw(epoch, perm, n_neg=M)[2][:check].cpu().numpy()
+        want = sampler.sample_numpy(c._user, c._item, order, 0, check, c._rowptr, c._pos_items, U,
+                                    I, args.seed, epoch, n_neg=M)[2]
+        assert np.array_equal(got, want), f"device draw differs from the numpy path at n_neg={M}"
+        del got
+    times = {M: [] for M in variants}
+    for _ in range(args.reps):
+        for M in variants:
+            times[M] += device_ms(lambda: s.draw(epoch, perm, n_neg=M), 1)
+    med = {M: float(np.median(v)) for M, v in times.items()}
+    result = {
+        "config": cfg["name"], "interactions": E, "users": U, "items": I, "reps": args.reps,
+        "device_draw_ms_shuffled": {"one_negative" if M is None else f"n_neg_{M}": round(v, 3)
+                                    for M, v in med.items()},
+        "device_draw_ms_all": {"one_negative" if M is None else f"n_neg_{M}":
+                               [round(x, 3) for x in v] for M, v in times.items()},
+        "draw_bytes": {f"n_neg_{M}": E * (2 + M) * 8 for M in args.n_neg},
+        "device_equals_numpy_first_slots": check,
+        "what": ("one whole-epoch BprSampler.draw(order=randperm, n_neg=M) between events, the "
+                 "variants interleaved rep by rep, median of reps; the output allocation "
+                 "(torch.empty) is inside the timed region, as in a training epoch"),
+    }
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
@@ -79,6 +118,9 @@ def main():
     ap.add_argument("--subset", type=int, default=200_000)
     ap.add_argument("--check", type=int, default=1_000_000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--n-neg", type=int, nargs="+", default=None, metavar="M",
+                    help="time only the device draw with M negatives per sample (several values: "
+                         "interleaved), one negative beside them")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("sampler_bench: needs a HIP device")
@@ -97,6 +139,9 @@ def main():
     build_s = time.perf_counter() - t0
     bench.log(f"[sampler_bench] device sampler built in {build_s:.1f}s")
     epoch = 1
+    if args.n_neg:
+        multi_neg(args, s, users, items, U, I, E, epoch, cfg)
+        return
     s.draw(epoch)  # warm-up
     perm = s.permutation(epoch)
     s.draw(epoch, perm)
