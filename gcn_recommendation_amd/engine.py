@@ -233,7 +233,13 @@ ABI = [
                                              _P, _P]),
     ("lgcn_bpr_select_hardest", ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _I32, _I32,
                                                _I32, _P, _P, _P]),
-    ("lgcn_fusion_prelayer", ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
+    ("lgcn_ssm_loss", ctypes.c_int, [_P, _I64] * 6 + [_P, _I32, _I32, _I32, ctypes.c_float,
+                                                      ctypes.c_float, _P, _P, _P, _P, _P]),
+    ("lgcn_ssm_loss_indexed", ctypes.c_int, [_P, _I64] * 4 + [_I64, _I64, _P, _P, _P, _I32, _I32,
+                                                              _I32, ctypes.c_float, ctypes.c_float,
+                                                              _P, _P, _P, _P, _P]),
+    ("lgcn_ssm_keys", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I64, _I64, _P, _P]),
+    ("lgcn_fusion_prelayer",ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
     ("lgcn_fusion_prelayer_backward_scratch_bytes", ctypes.c_size_t, [_I32, _I32, _I32]),
     ("lgcn_fusion_prelayer_backward", ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32,

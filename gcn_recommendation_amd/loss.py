@@ -10,6 +10,8 @@ call with the brand term fused into the launch (lgcn_bpr_brand_loss). Arithmetic
 + 1e-8)), L2 of the layer-0 rows / batch size; fp32 reductions, so GPU parity with the
 reference is a tolerance (tests/test_gpu_parity.py::test_fused_bpr_loss_vs_torch).
 """
+import numbers
+
 import torch
 
 from . import engine
@@ -154,3 +156,115 @@ def bpr_brand_loss_reg(final_user_emb, final_pos_item_emb, final_neg_item_emb,
                                       initial_neg_item_emb, final_brand_emb[pi],
                                       final_brand_emb[ni], ok.to(torch.uint8), float(lambda_reg),
                                       float(brand_loss_weight))
+
+
+class SSMLossFunction(torch.autograd.Function):
+    """BPRLossFunction's sibling for the sampled-softmax loss (lgcn_ssm_loss): (u, p, n, u0, p0,
+    n0, valid, lambda, temperature) with n / n0 the [B, M, d] candidate blocks and valid a uint8
+    [B, M] mask or None; the six gradient blocks come from the same launch."""
+
+    @staticmethod
+    def forward(ctx, u, p, n, u0, p0, n0, valid, lambda_reg, temperature):
+        lib = engine.load_library()
+        B, d = u.shape
+        if n.dim() != 3 or int(n.shape[0]) != B or not 1 <= int(n.shape[1]) <= engine.BPR_MAX_NEG:
+            raise engine.LgcnError("ssm_loss: the negatives must be a [B, M, d] block, 1 <= M <= "
+                                   f"{engine.BPR_MAX_NEG}, got {tuple(n.shape)}")
+        M = int(n.shape[1])
+        dev = u.device
+        rows = [t.detach() for t in (u, p, u0, p0)]
+        for t in rows:
+            if t.shape != (B, d) or t.dtype != torch.float32 or t.stride(1) != 1 or \
+                    t.device != dev:
+                raise engine.LgcnError("ssm_loss: four [B x d] fp32 row-major blocks expected")
+        blocks = [t.detach() for t in (n, n0)]
+        for t in blocks:
+            if t.shape != (B, M, d) or t.dtype != torch.float32 or t.stride(2) != 1 or \
+                    t.stride(0) != M * t.stride(1) or t.device != dev:
+                raise engine.LgcnError("ssm_loss: two [B, M, d] fp32 blocks with evenly strided "
+                                       "rows expected")
+        if valid is not None and (valid.shape != (B, M) or valid.dtype != torch.uint8 or
+                                  valid.device != dev or not valid.is_contiguous()):
+            raise engine.LgcnError("ssm_loss: valid must be a contiguous uint8 [B, M] tensor")
+        terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((2, (2 + M) * B, d), dtype=torch.float32, device=dev)
+        xu, xp, xu0, xp0 = rows
+        args = []
+        for t, ld in ((xu, xu.stride(0)), (xp, xp.stride(0)), (blocks[0], blocks[0].stride(1)),
+                      (xu0, xu0.stride(0)), (xp0, xp0.stride(0)),
+                      (blocks[1], blocks[1].stride(1))):
+            args += [engine._ptr(t), ld]
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_ssm_loss(*args, engine._ptr(valid), B, M, d, float(lambda_reg),
+                                            float(temperature), engine._ptr(terms),
+                                            engine._ptr(loss), engine._ptr(grads), None,
+                                            engine._stream(dev)), "lgcn_ssm_loss")
+        ctx.save_for_backward(grads)
+        ctx.dims = (B, M, d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grads,) = ctx.saved_tensors
+        B, M, d = ctx.dims
+        sg = grads * g
+        out = []
+        for half in (1, 0):  # the final rows, then the layer-0 rows
+            out += [sg[half, :B], sg[half, B:2 * B], sg[half, 2 * B:].view(B, M, d)]
+        return tuple(out) + (None, None, None)
+
+
+def _check_temperature(temperature, what):
+    if isinstance(temperature, bool) or not isinstance(temperature, numbers.Real) or \
+            not temperature > 0 or temperature == float("inf"):
+        raise ValueError(f"{what}: temperature={temperature!r} (a finite number > 0)")
+    return float(temperature)
+
+
+def ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb, initial_user_emb,
+                   initial_pos_item_emb, initial_neg_item_emb, lambda_reg, temperature=1.0,
+                   valid=None):
+    """The sampled-softmax loss as a torch expression, in the dtype of its inputs: what a CPU
+    adjacency runs, and the reference the HIP kernel is measured against."""
+    u, p, n = final_user_emb, final_pos_item_emb, final_neg_item_emb
+    u0, p0, n0 = initial_user_emb, initial_pos_item_emb, initial_neg_item_emb
+    pos_scores = torch.sum(u * p, dim=1)
+    neg_scores = torch.sum(u.unsqueeze(1) * n, dim=-1)
+    if valid is not None:
+        on = valid.bool()
+        keep = on.any(1)  # a sample without a valid candidate is skipped whole
+        neg_scores = neg_scores.masked_fill(~on, float("-inf"))
+        n0 = n0 * on.unsqueeze(-1).to(n0.dtype)
+        u0 = u0 * keep.unsqueeze(-1).to(u0.dtype)
+        p0 = p0 * keep.unsqueeze(-1).to(p0.dtype)
+    logits = torch.cat([pos_scores.unsqueeze(1), neg_scores], dim=1) / temperature
+    ssm = torch.mean(torch.logsumexp(logits, dim=1) - logits[:, 0])
+    reg = lambda_reg * (u0.norm(2).pow(2) + p0.norm(2).pow(2) + n0.norm(2).pow(2)) / float(len(u))
+    return ssm + reg
+
+
+def ssm_loss_reg(final_user_emb, final_pos_item_emb, final_neg_item_emb,
+                 initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
+                 lambda_reg, temperature=1.0, valid=None):
+    """Sampled-softmax (InfoNCE) loss over all M negatives of a sample, plus bpr_loss_reg's L2
+    term: bpr_loss_reg's call with [B, M, d] negative blocks.
+
+        z_0 = <u, p> / temperature, z_m = <u, n_m> / temperature
+        loss = mean_b (logsumexp_j z_j - z_0) + lambda_reg * (|U0|^2 + |P0|^2 + |N0|^2) / B
+
+    valid (None = every entry): a uint8 or bool [B, M] mask; a candidate with valid == 0 is no
+    term of the softmax or of the regulariser, a sample without a valid candidate contributes
+    nothing; the means still divide by B. On a HIP device loss and all six input gradients come
+    from one launch (lgcn_ssm_loss, include/lgcn.h states its orders of summation); on CPU
+    tensors ssm_loss_torch runs."""
+    temperature = _check_temperature(temperature, "ssm_loss_reg")
+    if final_user_emb.device.type != "cuda":
+        return ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb,
+                              initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
+                              lambda_reg, temperature, valid)
+    if valid is not None and valid.dtype == torch.bool:
+        valid = valid.to(torch.uint8)
+    return SSMLossFunction.apply(final_user_emb, final_pos_item_emb, final_neg_item_emb,
+                                 initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
+                                 valid, float(lambda_reg), temperature)

@@ -31,6 +31,12 @@ kernel: lgcn_bpr_select_hardest runs between the propagation and the loss, on th
 is about to read, and scores a candidate by the loss kernel's own expression. The route composed
 of public calls (model(adj) under no_grad, gather, argmax, bpr_step) propagates twice.
 
+With negatives="softmax" the [B, M] candidates are all used: the sampled-softmax (InfoNCE) loss,
+one softmax per sample over its positive and its M candidates with a temperature
+(lgcn_ssm_loss_indexed, SsmStepFunction). A sample has 2 + M rows: the batch has (2+M)B
+destination keys (lgcn_ssm_keys) and 2(2+M)B gradient rows, where negatives="all" — pairwise BPR on
+the B*M expanded triples — has 3BM and 6BM. Bitwise the gathered route through loss.ssm_loss_reg.
+
 `bpr_epoch` is the loop around it (main.py:488-531): the batches are views of one device-side draw
 of sampler.BprSampler, the per-batch losses come back as one device tensor.
 """
@@ -40,7 +46,7 @@ import weakref
 import torch
 
 from . import engine
-from .loss import bpr_loss_reg
+from .loss import _check_temperature, bpr_loss_reg, ssm_loss_torch
 
 
 class _Workspace:
@@ -392,6 +398,99 @@ class BprBrandStepFunction(torch.autograd.Function):
         return (None,) * 10 + blocks + ((gi,) if n_e0 == 1 else ())
 
 
+class SsmStepFunction(torch.autograd.Function):
+    """(graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, n_e0, *segments) ->
+    the sampled-softmax loss over all M candidates of cand [B, M] (loss.ssm_loss_reg's
+    expression), segments as BprStepFunction's.
+
+    BprStepFunction with 2 + M rows per sample: lgcn_ssm_loss_indexed reads them from the output
+    buffer and the layer-0 tables and keeps grads = [2 x (2+M)B x d] (layer-0 half, final half,
+    one row layout); the batch has (2+M)B destination keys (lgcn_ssm_keys), sorted once. A user
+    row and a positive row are read, differentiated and scattered once per sample, not M times."""
+
+    @staticmethod
+    def forward(ctx, graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, n_e0,
+                *segments):
+        if n_e0 not in (1, 2):
+            raise engine.LgcnError(f"bpr_step: n_e0={n_e0} (1 or 2)")
+        nseg = len(segments) - (2 - n_e0)
+        if nseg < 2:
+            raise engine.LgcnError("bpr_step: user and item segments expected")
+        lib = engine.load_library()
+        dev = graph.device
+        segs = [t.detach() for t in segments[:nseg]]
+        sizes = [int(t.shape[0]) for t in segs]
+        U, I = sizes[0], sizes[1]
+        out = engine.propagate_forward(graph, segs, K, hub_threshold)
+        d = int(out.shape[1])
+        i0 = segs[1] if n_e0 == 2 else segments[nseg].detach()
+        if i0.shape != (I, d) or i0.dtype != torch.float32 or i0.device != dev or \
+                (I > 0 and i0.stride(1) != 1):
+            raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
+        B, M = int(cand.shape[0]), int(cand.shape[1])
+        fu, fi, u0 = out[:U], out[U:U + I], segs[0]
+        terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((2, (2 + M) * B, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_ssm_loss_indexed(
+                engine._ptr(fu), d, engine._ptr(fi), d, engine._ptr(u0), d, engine._ptr(i0),
+                i0.stride(0) if I else d, U, I, engine._ptr(users), engine._ptr(pos),
+                engine._ptr(cand), B, M, d, float(lambda_reg), float(temperature),
+                engine._ptr(terms), engine._ptr(loss), engine._ptr(grads), None,
+                engine._stream(dev)), "lgcn_ssm_loss_indexed")
+        ctx.save_for_backward(grads, users, pos, cand)
+        ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
+        ctx.sizes, ctx.n_e0 = sizes, n_e0
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads, users, pos, cand = ctx.saved_tensors
+        graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
+        U, I = sizes[0], sizes[1]
+        _, m, d = grads.shape
+        B, M = int(cand.shape[0]), int(cand.shape[1])
+        lib = engine.load_library()
+        dev = graph.device
+        sg = grads * g  # SSMLossFunction.backward's scaling: [0] the layer-0 half, [1] the final
+        ws = _workspace(graph, d)
+        gi = None
+        with torch.cuda.device(dev):
+            stream = engine._stream(dev)
+            if ws.dirty:
+                ws.rezero()
+            n_keys = 2 * (U + I) + 1
+            ws.sort_scratch(lib, m, n_keys, stream)
+            engine._check(lib.lgcn_ssm_keys(engine._ptr(users), engine._ptr(pos),
+                                            engine._ptr(cand), B, M, U, I, engine._ptr(ws.keys),
+                                            stream), "lgcn_ssm_keys")
+            b = ws.i32
+            nbytes = ctypes.c_size_t(ws.temp_bytes)
+            engine._check(lib.lgcn_coo_sort_perm(engine._ptr(ws.keys), m, n_keys, engine._ptr(b[0]),
+                                                 engine._ptr(b[1]), engine._ptr(b[2]),
+                                                 engine._ptr(b[3]), engine._ptr(ws.temp),
+                                                 ctypes.byref(nbytes), stream),
+                          "lgcn_coo_sort_perm")
+            ws.dirty = True
+            _scatter(lib, ws, m, sg[1], 0, U + I, ws.G, engine.LGCN_SCATTER_STORE, ws.mask,
+                     ws.count, stream)
+            g0 = engine.propagate_backward(graph, ws.G, ctx.K, ctx.hub_threshold,
+                                           nz=(ws.mask, ws.count))
+            _scatter(lib, ws, m, sg[0], 0, U + I if n_e0 == 2 else U, g0,
+                     engine.LGCN_SCATTER_ADD, None, None, stream)
+            if n_e0 == 1:
+                gi = torch.zeros((I, d), dtype=torch.float32, device=dev)
+                _scatter(lib, ws, m, sg[0], U, U + I, gi, engine.LGCN_SCATTER_STORE, None, None,
+                         stream)
+            engine._check(lib.lgcn_rows_clear(engine._ptr(b[1]), m, 0, U + I, engine._ptr(ws.G), d,
+                                              d, engine._ptr(ws.mask), engine._ptr(ws.count),
+                                              stream), "lgcn_rows_clear")
+            ws.dirty = False
+        blocks = tuple(torch.split(g0, sizes, 0))
+        return (None,) * 9 + blocks + ((gi,) if n_e0 == 1 else ())
+
+
 def _check_item_brand(item_brand, num_items, device):
     if not torch.is_tensor(item_brand) or item_brand.dtype != torch.int32:
         raise engine.LgcnError("bpr_step: item_brand must be an int32 tensor (data.item_brand_map),"
@@ -443,7 +542,8 @@ def _cpu_loss(tables, users, pos, neg, lambda_reg, item_brand, brand_loss_weight
 
 
 def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, item_brand=None,
-             brand_loss_weight=0.1, negatives="hardest", return_negatives=False):
+             brand_loss_weight=0.1, negatives="hardest", return_negatives=False,
+             temperature=1.0):
     """The loss of one BPR batch (main.py:495-522) as a tensor whose
     `.backward()` leaves exactly the parameter `.grad`s main.py's route leaves:
 
@@ -481,8 +581,22 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
       negatives="all"  BPR over the B*M pairs: by definition the step on
           users.repeat_interleave(M), pos.repeat_interleave(M), neg.reshape(-1) — main.py's
           formula on the expanded triples (its means divide by B*M).
+      negatives="softmax"  the sampled-softmax (InfoNCE) loss: one softmax per sample over its
+          positive and all M candidates, logits divided by `temperature` (a finite number > 0,
+          else ValueError), plus the L2 term over the sample's 2 + M layer-0 rows; both means
+          divide by B (loss.ssm_loss_reg states the expression). One propagation, then
+          lgcn_ssm_loss_indexed on views of its output: a user row and a positive row are read,
+          differentiated and scattered once per sample, and the batch has (2+M)B scatter keys
+          where "all" has 3BM. Loss and `.grad`s are bitwise those of the gathered route (model(adj),
+          fu[users], fi[pos], fi[neg.reshape(-1)].view(B, M, d), the same of the layer-0 tables,
+          loss.ssm_loss_reg, backward). A candidate outside [0, items) (the sampler's -1) is no
+          term of the softmax or of the regulariser; a sample without one in range is skipped.
+          With item_brand (and a weight != 0) it raises LgcnError before any launch: the brand
+          term has no softmax form here. On a CPU adjacency the torch expression runs and a
+          candidate out of range raises LgcnError.
     Any other value raises ValueError. return_negatives=True returns (loss, neg_used), the int64
-    negatives the loss ran on: [B] for "hardest" (and for a 1-D neg, neg itself), [B*M] for "all".
+    negatives the loss ran on: [B] for "hardest" (and for a 1-D neg, neg itself), [B*M] for "all",
+    neg as given for "softmax". With a 1-D neg neither negatives nor temperature is looked at.
     check_indices=True validates every entry of a 2-D neg. On a CPU adjacency model(adj) runs
     once, the candidates are scored and chosen with torch ops by the same rule
     (select_hardest_torch) and the reference expression runs on the choice; a sample without a
@@ -496,8 +610,14 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
     if brand:
         _check_item_brand(item_brand, I, adj.device)
     many = neg.dim() == 2
-    if many and negatives not in ("hardest", "all"):
-        raise ValueError(f"bpr_step: negatives={negatives!r} ('hardest' or 'all')")
+    if many and negatives not in ("hardest", "all", "softmax"):
+        raise ValueError(f"bpr_step: negatives={negatives!r} ('hardest', 'all' or 'softmax')")
+    softmax = many and negatives == "softmax"
+    if softmax:
+        temperature = _check_temperature(temperature, "bpr_step")
+        if brand:
+            raise engine.LgcnError("bpr_step: negatives='softmax' has no brand term (item_brand "
+                                   "must be None or brand_loss_weight 0)")
     if check_indices:
         for name, t, n in (("users", users, U), ("pos", pos, I), ("neg", neg, I)):
             if bool(((t < 0) | (t >= n)).any()):
@@ -508,7 +628,17 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
                         neg.reshape(-1), lambda_reg, item_brand=item_brand,
                         brand_loss_weight=brand_loss_weight, return_negatives=return_negatives)
     if adj.device.type != "cuda":
+        if softmax and bool(((neg < 0) | (neg >= I)).any()):
+            raise engine.LgcnError("bpr_step: a candidate negative is out of range; the CPU "
+                                   "route cannot leave it out of the softmax")
         tables = model(adj)
+        if softmax:
+            fu, fi, _, u0, i0 = tables
+            B, M = neg.shape
+            flat = neg.reshape(-1)
+            loss = ssm_loss_torch(fu[users], fi[pos], fi[flat].view(B, M, -1), u0[users], i0[pos],
+                                  i0[flat].view(B, M, -1), lambda_reg, temperature)
+            return (loss, neg) if return_negatives else loss
         if many:
             neg, found = select_hardest_torch(tables[0], tables[1], users, neg)
             if not bool(found.all()):
@@ -525,6 +655,11 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
         tensors = [model.user_embedding.weight, model.fused_item_embedding(),
                    model.brand_embedding.weight, model.item_id_embedding.weight]
     graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
+    if softmax:
+        loss = SsmStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                     float(lambda_reg), temperature, users, pos, neg, n_e0,
+                                     *tensors)
+        return (loss, neg) if return_negatives else loss
     if brand:
         out = BprBrandStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
                                          float(lambda_reg), float(brand_loss_weight), users, pos,
@@ -537,7 +672,8 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
 
 
 def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
-              item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest"):
+              item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
+              temperature=1.0):
     """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
     epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
     batch
@@ -556,17 +692,22 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
 
     n_neg (None = the epoch above; an integer in [1, 64]) is passed to sampler.epoch: the draw
     holds n_neg candidate negatives per sample and every batch's neg is [batch, n_neg]; negatives
-    ("hardest" or "all") is bpr_step's and says what the step does with them."""
+    ("hardest", "all" or "softmax") is bpr_step's and says what the step does with them;
+    temperature is the softmax step's."""
     if sampler.device != adj.device:
         raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
-    if n_neg is not None and negatives not in ("hardest", "all"):
-        raise ValueError(f"bpr_epoch: negatives={negatives!r} ('hardest' or 'all')")
+    if n_neg is not None and negatives not in ("hardest", "all", "softmax"):
+        raise ValueError(f"bpr_epoch: negatives={negatives!r} ('hardest', 'all' or 'softmax')")
+    if n_neg is not None and negatives == "softmax":
+        temperature = _check_temperature(temperature, "bpr_epoch")
+        if item_brand is not None and brand_loss_weight != 0:
+            raise engine.LgcnError("bpr_epoch: negatives='softmax' has no brand term")
     # the draw is made here
     batches = sampler.epoch(epoch, batch_size, shuffle=shuffle, n_neg=n_neg)
     if adj.device.type != "cuda" and int(sampler.unsampled.item()):
         raise engine.LgcnError("bpr_epoch: a user has every item as a positive (no negative to "
                                "draw); the CPU route cannot skip the sample")
-    many = {} if n_neg is None else {"negatives": negatives}
+    many = {} if n_neg is None else {"negatives": negatives, "temperature": temperature}
     losses = []
     for users, pos, neg in batches:
         optimizer.zero_grad()

@@ -63,8 +63,9 @@ extern "C" {
  * structs, LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK) and the wide recommendation lists
  * (lgcn_score_topk_wide, lgcn_topk_wide_splits, its scratch query, LGCN_TOPK_WIDE_MAX_K) and
  * several negatives per sample (lgcn_bpr_sample_multi, lgcn_bpr_select_hardest,
- * LGCN_BPR_MAX_NEG) were added without a bump: purely additive, no existing symbol, struct or
- * constant changed. */
+ * LGCN_BPR_MAX_NEG) and the sampled-softmax loss over them (lgcn_ssm_loss,
+ * lgcn_ssm_loss_indexed, lgcn_ssm_keys) were added without a bump: purely additive, no existing
+ * symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -883,6 +884,67 @@ int lgcn_bpr_select_hardest(const float* fu, int64_t ld_fu, const float* fi, int
                             int64_t n_users, int64_t n_items, const int64_t* users,
                             const int64_t* cand, int32_t B, int32_t n_neg, int32_t d,
                             int64_t* neg_out, float* score_out, void* stream);
+
+/* ---- sampled-softmax loss over all M candidate negatives of a sample ------------------------- */
+/* One softmax per sample over its positive and its M candidates (1 <= M <= LGCN_BPR_MAX_NEG),
+ * temperature tau > 0, plus lgcn_bpr_loss's L2 term over the 2 + M layer-0 rows of the sample:
+ *   z_0 = <u,p> / tau, z_m = <u,n_m> / tau
+ *   L_b = log(sum_j exp(z_j - z_max)) + (z_max - z_0),  j over 0 and the valid m
+ *   *loss = mean_b L_b + lambda * (|U0|^2 + |P0|^2 + |N0|^2) / B
+ * Rows: u, p, u0, p0 [B x d]; n, n0 [B*M x d], row b * M + m = candidate m of sample b (a
+ * contiguous [B, M, d] block). valid (NULL = every entry): uint8 [B x M]; a candidate with
+ * valid == 0 is no term of the softmax or of the regulariser, its rows are not read and its two
+ * gradient rows are +0. A sample without a valid candidate is skipped: zero terms, +0 gradient
+ * rows, zero coefficients, nothing of it read. Both means divide by B whatever was skipped.
+ * Orders, all fp32, one wave per sample:
+ *  - a score <u,v> is lgcn_bpr_select_hardest's (per lane an fmaf chain over k = lane, lane + 64,
+ *    ... from +0, then the 32, 16, ..., 1 xor butterfly); z = fp32(score * it), it = fp32(1 / tau);
+ *  - z_max = the maximum over z_0 and the valid z_m; e_j = expf(z_j - z_max);
+ *    Z = fp32(e_0 + S), S = the xor butterfly sum over the 64 lanes, lane m holding e_m (+0 for
+ *    m >= M or an invalid candidate); L_b = fp32(logf(Z) + fp32(z_max - z_0));
+ *  - c = fp32(it / B); g_0 = fp32(fp32(fp32(e_0 / Z) - 1) * c), g_m = fp32(fp32(e_m / Z) * c);
+ *  - du[k] = one chain from fp32(g_0 * p[k]), then fmaf(g_m, n_m[k], .) over the valid m in
+ *    ascending m; dp = g_0 * u, dn_m = g_m * u; d(row0) = fp32(fp32(2 * lambda) / B) * row0;
+ *  - squared norms: per lane one fmaf chain from +0 — over k = lane, lane + 64, ... u0[k]^2 then
+ *    p0[k]^2, then each valid candidate's row in ascending m, each over k — then the butterfly;
+ *  - *loss = fp32(sl / B) + fp32(fp32(lambda * sr) / B), sl / sr the sums of L_b / of the squared
+ *    norms in lgcn_bpr_loss's fixed batch order (256 strided partial sums, then a halving tree).
+ * No float atomics: run-to-run identical.
+ * grads = [2 x (2+M)B x d]: half 0 the layer-0 gradient rows, half 1 the final ones; inside a
+ * half rows [0, B) users, [B, 2B) positives, 2B + b * M + m candidate m of sample b. One
+ * permutation of lgcn_ssm_keys' (2+M)B keys therefore indexes either half as lgcn_rows_scatter's
+ * source. terms: scratch [2 x B]. coef (NULL = not wanted): [B x (1+M)], g_0, g_1..g_M per
+ * sample, 0 for invalid entries.
+ * LGCN_EINVAL before any launch: a NULL pointer other than valid / coef / stream, B < 1, d < 1,
+ * ld < d, M outside [1, LGCN_BPR_MAX_NEG], (2+M) * B past int32, tau not finite or <= 0. */
+int lgcn_ssm_loss(const float* u, int64_t ldu, const float* p, int64_t ldp, const float* n,
+                  int64_t ldn, const float* u0, int64_t ldu0, const float* p0, int64_t ldp0,
+                  const float* n0, int64_t ldn0, const uint8_t* valid, int32_t B, int32_t M,
+                  int32_t d, float lambda, float temperature, float* terms, float* loss,
+                  float* grads, float* coef, void* stream);
+
+/* lgcn_ssm_loss with the rows read from the tables (lgcn_bpr_loss_indexed's four): users / pos
+ * int64 [B], cand int64 [B x M] row-major (lgcn_bpr_sample_multi's neg). A candidate outside
+ * [0, n_items) (the sampler's -1) is invalid; a sample whose user or positive lies outside its
+ * table, or without a valid candidate, is skipped; nothing of either is dereferenced. The same
+ * kernel body: bitwise lgcn_ssm_loss's outputs on gathered copies with the matching valid mask.
+ * Also LGCN_EINVAL: n_users or n_items < 0. */
+int lgcn_ssm_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                          const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                          int64_t n_users, int64_t n_items, const int64_t* users,
+                          const int64_t* pos, const int64_t* cand, int32_t B, int32_t M,
+                          int32_t d, float lambda, float temperature, float* terms, float* loss,
+                          float* grads, float* coef, void* stream);
+
+/* The (2+M)B destination keys of that batch's gradient rows, keys int64 in grads' row order:
+ * lgcn_bpr_keys' numbering (2 * row, bit 0 set for a candidate's row). "None" =
+ * 2 * (n_users + n_items): every key of a skipped sample, the key of an invalid candidate. Sort
+ * with n_keys = none + 1; the stable sort then sums a destination row's negative run in
+ * ascending (b, m) and its positive run in ascending b, autograd's index_put order for the 1-D
+ * gather indices users, pos and cand.reshape(-1). LGCN_EINVAL: lgcn_bpr_keys' limits, M outside
+ * [1, LGCN_BPR_MAX_NEG], (2+M) * B past int32. */
+int lgcn_ssm_keys(const int64_t* users, const int64_t* pos, const int64_t* cand, int32_t B,
+                  int32_t M, int64_t n_users, int64_t n_items, int64_t* keys, void* stream);
 
 /* ---- LightGCN_Fusion item pre-layer (models/lightgcn_fusion.py:45-49) ------------------------ */
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,

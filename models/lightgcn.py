@@ -113,18 +113,21 @@ class LightGCN(nn.Module):
     _bpr_n_e0 = 2  # the regulariser's user and item rows come from the propagation's segments
 
     def bpr_step(self, adj, users, pos, neg, lambda_reg, *, item_brand=None,
-                 brand_loss_weight=0.1, negatives="hardest", return_negatives=False):
+                 brand_loss_weight=0.1, negatives="hardest", return_negatives=False,
+                 temperature=1.0):
         """The BPR + L2 loss of one batch (main.py:495-522) in one call that keeps the batch
         indices: `.backward()` leaves the `.grad`s of the hand-written route, to the bit
         (train.bpr_step). item_brand (data.item_brand_map) adds the brand loss. A [B, M] neg
         holds M candidate negatives per sample: negatives="hardest" trains on the one the model
-        scores highest, chosen inside the step; "all" on every pair."""
+        scores highest, chosen inside the step; "all" on every pair; "softmax" on the
+        sampled-softmax loss over all M with logits divided by `temperature`."""
         return train.bpr_step(self, adj, users, pos, neg, lambda_reg, item_brand=item_brand,
                               brand_loss_weight=brand_loss_weight, negatives=negatives,
-                              return_negatives=return_negatives)
+                              return_negatives=return_negatives, temperature=temperature)
 
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
-                  item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest"):
+                  item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
+                  temperature=1.0):
         """One epoch of bpr_step batches over one device-side draw of the sampler
         (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
         `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
@@ -133,7 +136,7 @@ class LightGCN(nn.Module):
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
                                brand_loss_weight=brand_loss_weight, n_neg=n_neg,
-                               negatives=negatives)
+                               negatives=negatives, temperature=temperature)
 
     def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
         """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass

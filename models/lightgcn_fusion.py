@@ -66,17 +66,20 @@ class LightGCN_Fusion(nn.Module):
     _bpr_n_e0 = 1  # only the user rows: the item segment is the pre-layer's output
 
     def bpr_step(self, adj, users, pos, neg, lambda_reg, *, item_brand=None,
-                 brand_loss_weight=0.1, negatives="hardest", return_negatives=False):
+                 brand_loss_weight=0.1, negatives="hardest", return_negatives=False,
+                 temperature=1.0):
         """The BPR + L2 loss of one batch in one call that keeps the batch indices
         (train.bpr_step): the item segment is the pre-layer's output and keeps its autograd
         graph, the item regulariser rows come from item_id_embedding.weight. A [B, M] neg holds
-        M candidate negatives per sample (negatives="hardest" or "all", as LightGCN.bpr_step)."""
+        M candidate negatives per sample (negatives="hardest", "all" or "softmax" with its
+        `temperature`, as LightGCN.bpr_step)."""
         return train.bpr_step(self, adj, users, pos, neg, lambda_reg, item_brand=item_brand,
                               brand_loss_weight=brand_loss_weight, negatives=negatives,
-                              return_negatives=return_negatives)
+                              return_negatives=return_negatives, temperature=temperature)
 
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
-                  item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest"):
+                  item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
+                  temperature=1.0):
         """One epoch of bpr_step batches over one device-side draw of the sampler
         (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
         `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
@@ -85,7 +88,7 @@ class LightGCN_Fusion(nn.Module):
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
                                brand_loss_weight=brand_loss_weight, n_neg=n_neg,
-                               negatives=negatives)
+                               negatives=negatives, temperature=temperature)
 
     def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
         """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass

@@ -24,10 +24,17 @@ the plain one-negative step, the fused bpr_step(neg [B, M], negatives="hardest")
 composed of the one-negative API (model(adj) under no_grad, gather, argmax, bpr_step), forward +
 backward, in alternating blocks of one process (time_negatives).
 
+--negatives M --softmax [--temperature T] times the sampled-softmax step over all M candidates
+(time_softmax): the one-negative step, "hardest", "all", "softmax" and the autograd route of the
+softmax expression (model(adj), the gathers, loss.ssm_loss_torch, backward), forward + backward,
+in alternating blocks of one process; the first batch's fused loss and gradients are asserted
+bit-equal to the gathered route through loss.ssm_loss_reg.
+
 Prints one JSON line on stdout (progress goes to stderr).
 
     python tools/bpr_step_bench.py [--config c3] [--blocks 5] [--steps-per-block 4] [--brand-loss]
     python tools/bpr_step_bench.py --negatives 4
+    python tools/bpr_step_bench.py --negatives 16 --softmax --temperature 0.2
 """
 import argparse
 import contextlib
@@ -44,7 +51,8 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (CONFIGS, make_graph, xavier: the generator bench.py times)
 from gcn_recommendation_amd import engine  # noqa: E402
-from gcn_recommendation_amd.loss import bpr_brand_loss_reg, bpr_loss_reg  # noqa: E402
+from gcn_recommendation_amd.loss import (bpr_brand_loss_reg, bpr_loss_reg,  # noqa: E402
+                                         ssm_loss_reg, ssm_loss_torch)
 from models.lightgcn import LightGCN  # noqa: E402
 
 LAMBDA = 1e-4
@@ -160,11 +168,114 @@ def time_negatives(args, M, adj, m, U, I, dev, result):
     print(json.dumps(result), flush=True)
 
 
+def time_softmax(args, M, adj, models, U, I, dev, result):
+    """--negatives M --softmax: five routes in alternating blocks of whole forward + backward
+    steps (no optimizer: the tables stay put, so every route sees the same ones on every batch),
+      plain      the one-negative bpr_step on candidate 0;
+      hardest    bpr_step(neg [B, M], negatives="hardest");
+      all        bpr_step(neg [B, M], negatives="all"): BPR on the B*M expanded triples;
+      softmax    bpr_step(neg [B, M], negatives="softmax", temperature=T);
+      autograd   the same expression without the fused path: model(adj), the 2 * (2 + M) * B row
+                 gathers, loss.ssm_loss_torch, backward.
+    Before timing, the first batch's softmax loss and parameter gradients are asserted bit-equal
+    to the gathered route through loss.ssm_loss_reg (model(adj), the gathers, lgcn_ssm_loss)."""
+    T = args.temperature
+    m, other = models
+    rng = np.random.default_rng(1)
+    n_batches = args.blocks * args.steps_per_block + args.warmup
+    batches = [(torch.from_numpy(rng.integers(0, U, args.batch)).to(dev),
+                torch.from_numpy(rng.integers(0, I, args.batch)).to(dev),
+                torch.from_numpy(rng.integers(0, I, (args.batch, M))).to(dev))
+               for _ in range(n_batches)]
+
+    def gathered(m, users, pos, cand, reg):
+        fu, fi, fb, u0, i0 = m(adj, use_brand=False)
+        flat = cand.reshape(-1)
+        shape = (cand.shape[0], M, -1)
+        return reg(fu[users], fi[pos], fi[flat].view(shape), u0[users], i0[pos],
+                   i0[flat].view(shape), LAMBDA, T)
+
+    def plain(m, users, pos, cand):
+        return m.bpr_step(adj, users, pos, cand[:, 0].contiguous(), LAMBDA)
+
+    def mode(name):
+        return lambda m, users, pos, cand: m.bpr_step(adj, users, pos, cand, LAMBDA,
+                                                      negatives=name, temperature=T)
+
+    def autograd(m, users, pos, cand):
+        return gathered(m, users, pos, cand, ssm_loss_torch)
+
+    routes = (("plain", plain), ("hardest", mode("hardest")), ("all", mode("all")),
+              ("softmax", mode("softmax")), ("autograd_softmax", autograd))
+
+    first = batches[-1]
+    for x in (m, other):  # a model timed at another M before still holds its last gradients
+        x.zero_grad(set_to_none=True)
+    got = mode("softmax")(m, *first)
+    got.backward()
+    want = gathered(other, *first, ssm_loss_reg)
+    want.backward()
+    assert bits_equal(got, want), f"loss differs: {got.item()!r} vs {want.item()!r}"
+    ga, gb = dict(m.named_parameters()), dict(other.named_parameters())
+    for k in ga:
+        assert bits_equal(ga[k].grad, gb[k].grad), f"gradient of {k} differs"
+    torch_loss = autograd(other, *first).item()
+    bench.log(f"[bpr_step_bench] softmax M={M}: loss {got.item():.6f} and {len(ga)} gradients "
+              "bit-equal to the gathered route")
+    loss_rel_diff = abs(got.item() - torch_loss) / abs(torch_loss)
+    other.zero_grad(set_to_none=True)
+    del got, want
+
+    def step(fn, b):
+        m.zero_grad(set_to_none=True)
+        fn(m, *b).backward()
+
+    for name, fn in routes:
+        for b in batches[:args.warmup]:
+            step(fn, b)
+    per_block = {name: [] for name, _ in routes}
+    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for blk in range(args.blocks):
+        lo = args.warmup + blk * args.steps_per_block
+        for name, fn in routes:
+            torch.cuda.synchronize()
+            a.record()
+            for b in batches[lo:lo + args.steps_per_block]:
+                step(fn, b)
+            e.record()
+            torch.cuda.synchronize()
+            per_block[name].append(a.elapsed_time(e) / args.steps_per_block)
+    med = {name: float(np.median(v)) for name, v in per_block.items()}
+    spread = {name: float(np.ptp(v)) for name, v in per_block.items()}
+    result.update(
+        negatives=M, temperature=T, first_batch_bit_equal=True,
+        loss_rel_diff_vs_torch_expression=loss_rel_diff,
+        step_ms={name: round(v, 3) for name, v in med.items()},
+        step_block_ms={name: [round(x, 3) for x in v] for name, v in per_block.items()},
+        spread_ms={name: round(v, 3) for name, v in spread.items()},
+        all_minus_softmax_ms=round(med["all"] - med["softmax"], 3),
+        autograd_minus_softmax_ms=round(med["autograd_softmax"] - med["softmax"], 3),
+        softmax_minus_plain_ms=round(med["softmax"] - med["plain"], 3),
+        softmax_faster_than_all=bool(med["softmax"] < med["all"]),
+        softmax_faster_than_autograd=bool(med["softmax"] < med["autograd_softmax"]),
+        scatter_keys={"softmax": (2 + M) * args.batch, "all": 3 * M * args.batch},
+        what=("forward + backward of one batch, zero_grad before, no optimizer step; device "
+              "events around alternating blocks of steps per route, median over the blocks; "
+              "spread_ms = max - min of a route's block medians; plain = bpr_step on candidate 0, "
+              "hardest / all / softmax = bpr_step(neg [B, M], negatives=...), autograd_softmax = "
+              "model(adj) + gathers + loss.ssm_loss_torch + backward"))
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--negatives", type=int, nargs="+", default=None, metavar="M",
                     help="time the hardest-of-M step against the plain step and the composed "
                          "route (and nothing else); several M: one after the other on one graph")
+    ap.add_argument("--softmax", action="store_true",
+                    help="with --negatives: time the sampled-softmax step over all M candidates "
+                         "beside the plain, hardest and all steps and the autograd route")
+    ap.add_argument("--temperature", type=float, default=0.2, help="temperature of --softmax")
     ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
     ap.add_argument("--gen", default="powerlaw", choices=["powerlaw", "uniform"])
     ap.add_argument("--batch", type=int, default=2048)
@@ -193,6 +304,8 @@ def main():
                                   (n, n)).to(dev)
     nnz = len(v)
     del r, c, v
+    if args.softmax and not args.negatives:
+        sys.exit("bpr_step_bench: --softmax needs --negatives M")
     if args.negatives:
         if args.brand_loss or not all(1 <= M <= engine.BPR_MAX_NEG for M in args.negatives):
             sys.exit(f"bpr_step_bench: --negatives takes 1..{engine.BPR_MAX_NEG}, without "
@@ -201,7 +314,12 @@ def main():
         for M in args.negatives:   # one JSON line per M
             result = {"config": cfg["name"], "nnz": nnz, "d": d, "K": K, "batch": args.batch,
                       "blocks": args.blocks, "steps_per_block": args.steps_per_block}
-            time_negatives(args, M, adj, model, U, I, dev, result)
+            if args.softmax:
+                other = make_model(emb_host, U, I, d, K, dev)
+                time_softmax(args, M, adj, (model, other), U, I, dev, result)
+                del other
+            else:
+                time_negatives(args, M, adj, model, U, I, dev, result)
         return
     if args.brand_loss:
         if NB < 1:
