@@ -13,9 +13,11 @@ SRCS = [os.path.join(CSRC, f) for f in (
     "lgcn_layer_add_sparse.hip", "lgcn_layer_add_div.hip", "lgcn_layer_add.hip",
     "lgcn_layer_mean.hip", "lgcn_layer_store.hip", "lgcn_engine.hip", "lgcn_eval.hip",
     "lgcn_bpr.hip", "lgcn_bpr_step.hip", "lgcn_sampler.hip", "lgcn_fusion.hip",
-    "lgcn_fusion_bwd.hip", "lgcn_adam.hip", "lgcn_exact.hip", "lgcn_ssm.hip")]
+    "lgcn_fusion_bwd.hip", "lgcn_adam.hip", "lgcn_exact.hip", "lgcn_ssm.hip",
+    "lgcn_inbatch.hip")]
 HDRS = [os.path.join(ROOT, "include", "lgcn.h"), os.path.join(CSRC, "lgcn_kernels.h"),
-        os.path.join(CSRC, "lgcn_bpr_rows.h"), os.path.join(CSRC, "lgcn_ssm_rows.h")]
+        os.path.join(CSRC, "lgcn_bpr_rows.h"), os.path.join(CSRC, "lgcn_ssm_rows.h"),
+        os.path.join(CSRC, "lgcn_inbatch_rows.h")]
 OUT = os.path.join(_PKG, "liblgcn_engine.so")
 OBJ_DIR = os.path.join(_PKG, "_obj")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]

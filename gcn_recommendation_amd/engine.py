@@ -46,6 +46,8 @@ ABI_VERSION = 14
 LGCN_EMU_CANDS, LGCN_EMU_META_BYTES, LGCN_EMU_BLOCK = 16, 16, 256
 ADAM_MAX_TENSORS, ADAM_CHUNK = 16, 4096  # LGCN_ADAM_MAX_TENSORS, LGCN_ADAM_CHUNK
 BPR_MAX_NEG = 64  # LGCN_BPR_MAX_NEG: negatives per sample (lgcn_bpr_sample_multi, _select_hardest)
+# LGCN_INBATCH_MAX_B, _MAX_D, _MAX_COEF_B: the in-batch softmax loss (lgcn_inbatch_loss)
+INBATCH_MAX_B, INBATCH_MAX_D, INBATCH_MAX_COEF_B = 32768, 256, 4096
 
 # Rows up to this degree run as row bundles in the layer kernel (one sequential fmaf chain each,
 # bitwise = reference CPU path). Longer rows ("hubs") follow the hub mode:
@@ -239,6 +241,13 @@ ABI = [
                                                               _I32, ctypes.c_float, ctypes.c_float,
                                                               _P, _P, _P, _P, _P]),
     ("lgcn_ssm_keys", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I64, _I64, _P, _P]),
+    ("lgcn_inbatch_loss", ctypes.c_int, [_P, _I64] * 4 + [_P, _P, _P, _I32, _I32, ctypes.c_float,
+                                                          ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    ("lgcn_inbatch_loss_indexed", ctypes.c_int, [_P, _I64] * 4 + [_I64, _I64, _P, _P, _P, _P, _P,
+                                                                  _I32, _I32, ctypes.c_float,
+                                                                  ctypes.c_float, _P, _P, _P, _P,
+                                                                  _P, _P]),
+    ("lgcn_inbatch_keys", ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _P]),
     ("lgcn_fusion_prelayer",ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
                                             ctypes.c_float, _P, _I64, _P]),
     ("lgcn_fusion_prelayer_backward_scratch_bytes", ctypes.c_size_t, [_I32, _I32, _I32]),

@@ -268,3 +268,150 @@ def ssm_loss_reg(final_user_emb, final_pos_item_emb, final_neg_item_emb,
     return SSMLossFunction.apply(final_user_emb, final_pos_item_emb, final_neg_item_emb,
                                  initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
                                  valid, float(lambda_reg), temperature)
+
+
+# ---- in-batch softmax: a sample's negatives are the other samples' positives --------------------
+def inbatch_off_mask(users, pos, positives=None):
+    """off[b, c] of the in-batch softmax as a bool [B, B] (torch tensors in, a tensor on their
+    device out; numpy arrays in, an array out): column c is no true negative of row b when
+    pos[c] == pos[b] (the same item again), users[c] == users[b] (pos[c] is a known positive of
+    that user) or, with positives = (rowptr, items) — the sampler's sorted, de-duplicated per-user
+    lists (BprSampler.positives()) — pos[c] lies in the list of users[b] (a user outside the CSR
+    has no list). The diagonal is False: a sample's own positive is always a column of its row.
+    What lgcn_inbatch_loss_indexed derives on the device, stated with torch ops: for tests, for
+    the gathered route (inbatch_loss_reg) and for the CPU route."""
+    as_numpy = not torch.is_tensor(users)
+    users, pos = torch.as_tensor(users).long(), torch.as_tensor(pos).long()
+    B = int(users.shape[0])
+    off = (pos.unsqueeze(0) == pos.unsqueeze(1)) | (users.unsqueeze(0) == users.unsqueeze(1))
+    if positives is not None:
+        rowptr = torch.as_tensor(positives[0]).to(users.device).long()
+        items = torch.as_tensor(positives[1]).to(users.device).long()
+        n_users = int(rowptr.numel()) - 1
+        if n_users > 0 and items.numel() > 0:
+            ok = (users >= 0) & (users < n_users)
+            uc = users.clamp(0, n_users - 1)
+            lo = torch.where(ok, rowptr[uc], torch.zeros_like(uc))
+            hi = torch.where(ok, rowptr[uc + 1], torch.zeros_like(uc))
+            lo, hi = lo.unsqueeze(1).repeat(1, B), hi.unsqueeze(1).repeat(1, B)
+            target = pos.unsqueeze(0).expand(B, B)
+            found = torch.zeros((B, B), dtype=torch.bool, device=users.device)
+            while True:  # the kernel's binary search, every pair advanced one step per round
+                act = lo < hi
+                if not bool(act.any()):
+                    break
+                mid = (lo + hi) >> 1
+                v = items[mid.clamp(max=items.numel() - 1)]
+                found |= act & (v == target)
+                lo = torch.where(act & (v < target), mid + 1, lo)
+                hi = torch.where(act & (v >= target), mid, hi)
+            off |= found
+    off.fill_diagonal_(False)
+    return off.numpy() if as_numpy else off
+
+
+def inbatch_loss_torch(final_user_emb, final_pos_item_emb, initial_user_emb,
+                       initial_pos_item_emb, lambda_reg, temperature=1.0, off=None, valid=None,
+                       q=None):
+    """The in-batch softmax loss as a torch expression, in the dtype of its inputs: what a CPU
+    adjacency runs, and the reference the HIP kernels are measured against.
+
+        z_bc = <u_b, p_c> / temperature - q_c,   on(b, c) = (c == b) or not off[b, c]
+        loss = mean_b (logsumexp_{c on} z_bc - z_bb) + lambda_reg * (|U0|^2 + |P0|^2) / B
+
+    off: bool or uint8 [B, B] (inbatch_off_mask), its diagonal not looked at; valid: bool or
+    uint8 [B], a sample with valid == 0 is skipped — off as a column of every row, no term of its
+    own, no regulariser term; q: [B], the correction of column c. Both means divide by B."""
+    u, p, u0, p0 = final_user_emb, final_pos_item_emb, initial_user_emb, initial_pos_item_emb
+    B = int(u.shape[0])
+    logits = (u @ p.t()) / temperature
+    if q is not None:
+        logits = logits - q.to(logits.dtype).unsqueeze(0)
+    eye = torch.eye(B, dtype=torch.bool, device=u.device)
+    on = torch.ones((B, B), dtype=torch.bool, device=u.device)
+    if off is not None:
+        on = ~off.bool() | eye
+    keep = None
+    if valid is not None:
+        keep = valid.bool()
+        on = on & keep.unsqueeze(0) & keep.unsqueeze(1)
+        on = on | ~keep.unsqueeze(1)  # a skipped row: any finite logits, its term is dropped below
+    masked = logits.masked_fill(~on, float("-inf"))
+    terms = torch.logsumexp(masked, dim=1) - torch.diagonal(logits)
+    if keep is not None:
+        terms = torch.where(keep, terms, torch.zeros_like(terms))
+        u0 = u0 * keep.unsqueeze(-1).to(u0.dtype)
+        p0 = p0 * keep.unsqueeze(-1).to(p0.dtype)
+    reg = lambda_reg * (u0.norm(2).pow(2) + p0.norm(2).pow(2)) / float(B)
+    return torch.mean(terms) + reg
+
+
+class InBatchLossFunction(torch.autograd.Function):
+    """SSMLossFunction's sibling for the in-batch softmax loss (lgcn_inbatch_loss): (u, p, u0, p0,
+    off, valid, q, lambda, temperature) with off a uint8 [B, B] mask, valid a uint8 [B] mask and q
+    a float32 [B] correction, each or None; the four gradient blocks come from the same launches."""
+
+    @staticmethod
+    def forward(ctx, u, p, u0, p0, off, valid, q, lambda_reg, temperature):
+        lib = engine.load_library()
+        B, d = u.shape
+        dev = u.device
+        rows = [t.detach() for t in (u, p, u0, p0)]
+        for t in rows:
+            if t.shape != (B, d) or t.dtype != torch.float32 or t.stride(1) != 1 or \
+                    t.device != dev:
+                raise engine.LgcnError("inbatch_loss: four [B x d] fp32 row-major blocks expected")
+        if not 1 <= B <= engine.INBATCH_MAX_B or not 1 <= d <= engine.INBATCH_MAX_D:
+            raise engine.LgcnError(f"inbatch_loss: B={B}, d={d} (1 <= B <= "
+                                   f"{engine.INBATCH_MAX_B}, 1 <= d <= {engine.INBATCH_MAX_D})")
+        for name, t, shape, dt in (("off", off, (B, B), torch.uint8),
+                                   ("valid", valid, (B,), torch.uint8),
+                                   ("q", q, (B,), torch.float32)):
+            if t is not None and (t.shape != shape or t.dtype != dt or t.device != dev or
+                                  not t.is_contiguous()):
+                raise engine.LgcnError(f"inbatch_loss: {name} must be a contiguous {dt} tensor of "
+                                       f"shape {shape} on {dev}")
+        work = torch.empty(5 * B, dtype=torch.float32, device=dev)
+        mask = torch.empty(B * ((B + 31) // 32), dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((2, 2 * B, d), dtype=torch.float32, device=dev)
+        args = []
+        for t in rows:
+            args += [engine._ptr(t), t.stride(0)]
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_inbatch_loss(*args, engine._ptr(off), engine._ptr(valid),
+                                                engine._ptr(q), B, d, float(lambda_reg),
+                                                float(temperature), engine._ptr(work),
+                                                engine._ptr(mask), engine._ptr(loss),
+                                                engine._ptr(grads), None, engine._stream(dev)),
+                          "lgcn_inbatch_loss")
+        ctx.save_for_backward(grads)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grads,) = ctx.saved_tensors
+        B = grads.shape[1] // 2
+        sg = grads * g
+        return (sg[1, :B], sg[1, B:], sg[0, :B], sg[0, B:]) + (None,) * 5
+
+
+def inbatch_loss_reg(final_user_emb, final_pos_item_emb, initial_user_emb, initial_pos_item_emb,
+                     lambda_reg, temperature=1.0, off=None, valid=None, q=None):
+    """In-batch softmax loss plus bpr_loss_reg's L2 term over the batch's 2B layer-0 rows: sample
+    b's negatives are the positives of the other samples, less the columns off[b] names
+    (inbatch_off_mask); inbatch_loss_torch states the expression. On a HIP device loss and all
+    four input gradients come from lgcn_inbatch_loss (32 x 32 score tiles recomputed on the exact
+    f32 MFMA, no [B, B] logits in memory; include/lgcn.h states its orders of summation), for
+    B <= 32768 and d <= 256; on CPU tensors inbatch_loss_torch runs."""
+    temperature = _check_temperature(temperature, "inbatch_loss_reg")
+    if final_user_emb.device.type != "cuda":
+        return inbatch_loss_torch(final_user_emb, final_pos_item_emb, initial_user_emb,
+                                  initial_pos_item_emb, lambda_reg, temperature, off, valid, q)
+    if off is not None and off.dtype == torch.bool:
+        off = off.to(torch.uint8)
+    if valid is not None and valid.dtype == torch.bool:
+        valid = valid.to(torch.uint8)
+    return InBatchLossFunction.apply(final_user_emb, final_pos_item_emb, initial_user_emb,
+                                     initial_pos_item_emb, off, valid, q, float(lambda_reg),
+                                     temperature)

@@ -252,6 +252,7 @@ class BprSampler:
             self.device = torch.device("cuda", torch.cuda.current_device())
         rowptr, pos_items = mask_csr(users, items, num_users)
         self._n = int(users.size)
+        self._log_q = None
         host = (users.astype(np.int32), items.astype(np.int32), rowptr,
                 np.ascontiguousarray(pos_items, dtype=np.int32))
         if self.device.type == "cuda":
@@ -267,6 +268,29 @@ class BprSampler:
 
     def __len__(self):
         return self._n
+
+    def positives(self):
+        """(rowptr, items): the per-user sorted, de-duplicated positive lists the draw excludes,
+        int32 tensors on the sampler's device (rowptr of num_users + 1 entries) — what
+        train.inbatch_step takes as `positives` to drop a user's known positives from its
+        in-batch negatives."""
+        if self.device.type == "cuda":
+            return self._rowptr, self._pos_items
+        return torch.from_numpy(self._rowptr), torch.from_numpy(self._pos_items)
+
+    def item_log_q(self):
+        """float32 [num_items] on the sampler's device: log(count_i / n), count_i the number of
+        interactions (duplicates included) with item i and n their total — the logQ correction of
+        an in-batch softmax, whose negatives arrive in proportion to their popularity. Computed
+        in float64 on the host; an item without an interaction gets 0 (it is never a positive, so
+        never read). Cached."""
+        if self._log_q is None:
+            items = self._item.cpu().numpy() if torch.is_tensor(self._item) else self._item
+            count = np.bincount(items, minlength=self.num_items).astype(np.float64)
+            q = np.zeros(self.num_items, dtype=np.float64)
+            np.log(count / max(self._n, 1), out=q, where=count > 0)
+            self._log_q = torch.from_numpy(q.astype(np.float32)).to(self.device)
+        return self._log_q
 
     def draw(self, epoch, order=None, first=0, count=None, n_neg=None):
         """(users, pos, neg): int64 tensors on the sampler's device for output slots [0, count):

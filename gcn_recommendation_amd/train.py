@@ -37,6 +37,12 @@ one softmax per sample over its positive and its M candidates with a temperature
 destination keys (lgcn_ssm_keys) and 2(2+M)B gradient rows, where negatives="all" — pairwise BPR on
 the B*M expanded triples — has 3BM and 6BM. Bitwise the gathered route through loss.ssm_loss_reg.
 
+`inbatch_step` draws no negative at all: sample b's negatives are the positives of the other
+samples of its batch, less the ones that are no true negatives of its user (the in-batch softmax,
+lgcn_inbatch_loss_indexed, InBatchStepFunction). The [B, B] logits are recomputed tile by tile on
+the exact-f32 MFMA in each sweep and never stored; the batch has 2B rows and 2B destination keys
+(lgcn_inbatch_keys). Bitwise the gathered route through loss.inbatch_loss_reg.
+
 `bpr_epoch` is the loop around it (main.py:488-531): the batches are views of one device-side draw
 of sampler.BprSampler, the per-batch losses come back as one device tensor.
 """
@@ -46,7 +52,8 @@ import weakref
 import torch
 
 from . import engine
-from .loss import _check_temperature, bpr_loss_reg, ssm_loss_torch
+from .loss import (_check_temperature, bpr_loss_reg, inbatch_loss_torch, inbatch_off_mask,
+                   ssm_loss_torch)
 
 
 class _Workspace:
@@ -491,6 +498,102 @@ class SsmStepFunction(torch.autograd.Function):
         return (None,) * 9 + blocks + ((gi,) if n_e0 == 1 else ())
 
 
+class InBatchStepFunction(torch.autograd.Function):
+    """(graph, K, hub_threshold, lambda_reg, temperature, users, pos, rowptr, items, item_q, n_e0,
+    *segments) -> the in-batch softmax loss (loss.inbatch_loss_reg's expression with
+    loss.inbatch_off_mask(users, pos, (rowptr, items)) and q = item_q[pos]); rowptr / items and
+    item_q are device tensors or None, segments as BprStepFunction's.
+
+    SsmStepFunction with 2B rows and nothing drawn: lgcn_inbatch_loss_indexed reads the batch's
+    rows from the output buffer and the layer-0 tables and keeps grads = [2 x 2B x d] (layer-0
+    half, final half, one row layout); the batch has 2B destination keys (lgcn_inbatch_keys),
+    sorted once. The same workspace, STORE and ADD scatter and clear."""
+
+    @staticmethod
+    def forward(ctx, graph, K, hub_threshold, lambda_reg, temperature, users, pos, rowptr, items,
+                item_q, n_e0, *segments):
+        if n_e0 not in (1, 2):
+            raise engine.LgcnError(f"inbatch_step: n_e0={n_e0} (1 or 2)")
+        nseg = len(segments) - (2 - n_e0)
+        if nseg < 2:
+            raise engine.LgcnError("inbatch_step: user and item segments expected")
+        lib = engine.load_library()
+        dev = graph.device
+        segs = [t.detach() for t in segments[:nseg]]
+        sizes = [int(t.shape[0]) for t in segs]
+        U, I = sizes[0], sizes[1]
+        out = engine.propagate_forward(graph, segs, K, hub_threshold)
+        d = int(out.shape[1])
+        i0 = segs[1] if n_e0 == 2 else segments[nseg].detach()
+        if i0.shape != (I, d) or i0.dtype != torch.float32 or i0.device != dev or \
+                (I > 0 and i0.stride(1) != 1):
+            raise engine.LgcnError("inbatch_step: the item regulariser table must be [items x d] "
+                                   "fp32")
+        B = int(users.shape[0])
+        fu, fi, u0 = out[:U], out[U:U + I], segs[0]
+        work = torch.empty(5 * B, dtype=torch.float32, device=dev)
+        bits = torch.empty(B * ((B + 31) // 32), dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grads = torch.empty((2, 2 * B, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            engine._check(lib.lgcn_inbatch_loss_indexed(
+                engine._ptr(fu), d, engine._ptr(fi), d, engine._ptr(u0), d, engine._ptr(i0),
+                i0.stride(0) if I else d, U, I, engine._ptr(users), engine._ptr(pos),
+                engine._ptr(rowptr), engine._ptr(items), engine._ptr(item_q), B, d,
+                float(lambda_reg), float(temperature), engine._ptr(work), engine._ptr(bits),
+                engine._ptr(loss), engine._ptr(grads), None, engine._stream(dev)),
+                "lgcn_inbatch_loss_indexed")
+        ctx.save_for_backward(grads, users, pos)
+        ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
+        ctx.sizes, ctx.n_e0 = sizes, n_e0
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads, users, pos = ctx.saved_tensors
+        graph, sizes, n_e0 = ctx.graph, ctx.sizes, ctx.n_e0
+        U, I = sizes[0], sizes[1]
+        _, m, d = grads.shape
+        B = m // 2
+        lib = engine.load_library()
+        dev = graph.device
+        sg = grads * g  # InBatchLossFunction.backward's scaling: [0] the layer-0 half, [1] the final
+        ws = _workspace(graph, d)
+        gi = None
+        with torch.cuda.device(dev):
+            stream = engine._stream(dev)
+            if ws.dirty:
+                ws.rezero()
+            n_keys = 2 * (U + I) + 1
+            ws.sort_scratch(lib, m, n_keys, stream)
+            engine._check(lib.lgcn_inbatch_keys(engine._ptr(users), engine._ptr(pos), B, U, I,
+                                                engine._ptr(ws.keys), stream), "lgcn_inbatch_keys")
+            b = ws.i32
+            nbytes = ctypes.c_size_t(ws.temp_bytes)
+            engine._check(lib.lgcn_coo_sort_perm(engine._ptr(ws.keys), m, n_keys, engine._ptr(b[0]),
+                                                 engine._ptr(b[1]), engine._ptr(b[2]),
+                                                 engine._ptr(b[3]), engine._ptr(ws.temp),
+                                                 ctypes.byref(nbytes), stream),
+                          "lgcn_coo_sort_perm")
+            ws.dirty = True
+            _scatter(lib, ws, m, sg[1], 0, U + I, ws.G, engine.LGCN_SCATTER_STORE, ws.mask,
+                     ws.count, stream)
+            g0 = engine.propagate_backward(graph, ws.G, ctx.K, ctx.hub_threshold,
+                                           nz=(ws.mask, ws.count))
+            _scatter(lib, ws, m, sg[0], 0, U + I if n_e0 == 2 else U, g0,
+                     engine.LGCN_SCATTER_ADD, None, None, stream)
+            if n_e0 == 1:
+                gi = torch.zeros((I, d), dtype=torch.float32, device=dev)
+                _scatter(lib, ws, m, sg[0], U, U + I, gi, engine.LGCN_SCATTER_STORE, None, None,
+                         stream)
+            engine._check(lib.lgcn_rows_clear(engine._ptr(b[1]), m, 0, U + I, engine._ptr(ws.G), d,
+                                              d, engine._ptr(ws.mask), engine._ptr(ws.count),
+                                              stream), "lgcn_rows_clear")
+            ws.dirty = False
+        blocks = tuple(torch.split(g0, sizes, 0))
+        return (None,) * 11 + blocks + ((gi,) if n_e0 == 1 else ())
+
+
 def _check_item_brand(item_brand, num_items, device):
     if not torch.is_tensor(item_brand) or item_brand.dtype != torch.int32:
         raise engine.LgcnError("bpr_step: item_brand must be an int32 tensor (data.item_brand_map),"
@@ -671,9 +774,128 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
     return (loss, used) if return_negatives else loss
 
 
+def _check_inbatch_tensors(users, pos, device):
+    for name, t in (("users", users), ("pos", pos)):
+        if not torch.is_tensor(t) or t.dtype != torch.int64:
+            raise engine.LgcnError(f"inbatch_step: {name} must be an int64 tensor "
+                                   f"(got {getattr(t, 'dtype', type(t))})")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise engine.LgcnError(f"inbatch_step: {name} must be 1-D and contiguous, got "
+                                   f"{tuple(t.shape)}")
+        if t.device != device:
+            raise engine.LgcnError(f"inbatch_step: {name} on {t.device}, adjacency on {device}")
+    B = int(users.shape[0])
+    if int(pos.shape[0]) != B:
+        raise engine.LgcnError("inbatch_step: users and pos must have one length")
+    if not 1 <= B <= engine.INBATCH_MAX_B:
+        raise engine.LgcnError(f"inbatch_step: a batch of {B} (1 to {engine.INBATCH_MAX_B})")
+
+
+def _check_positives(positives, num_users, device):
+    """`positives` of inbatch_step as the (rowptr, items) pair the kernel takes."""
+    if hasattr(positives, "positives"):  # a sampler.BprSampler
+        if positives.num_users != num_users:
+            raise engine.LgcnError(f"inbatch_step: the sampler has {positives.num_users} users, "
+                                   f"the model {num_users}")
+        positives = positives.positives()
+    if not isinstance(positives, (tuple, list)) or len(positives) != 2:
+        raise engine.LgcnError("inbatch_step: positives must be a BprSampler or a (rowptr, items) "
+                               "pair")
+    rowptr, items = positives
+    for name, t in (("rowptr", rowptr), ("items", items)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or \
+                not t.is_contiguous():
+            raise engine.LgcnError(f"inbatch_step: positives {name} must be a contiguous 1-D "
+                                   f"int32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.device != device:
+            raise engine.LgcnError(f"inbatch_step: positives {name} on {t.device}, adjacency on "
+                                   f"{device}")
+    if int(rowptr.numel()) != num_users + 1:
+        raise engine.LgcnError(f"inbatch_step: positives rowptr must hold {num_users + 1} "
+                               f"entries, got {int(rowptr.numel())}")
+    if int(items.numel()) == 0:  # no list holds anything, and an empty tensor has no pointer
+        return None
+    return rowptr, items
+
+
+def _check_item_log_q(q, num_items, device):
+    if not torch.is_tensor(q) or q.dtype != torch.float32:
+        raise engine.LgcnError("inbatch_step: item_log_q must be a float32 tensor, got "
+                               f"{getattr(q, 'dtype', type(q))}")
+    if q.dim() != 1 or int(q.shape[0]) != num_items or not q.is_contiguous():
+        raise engine.LgcnError(f"inbatch_step: item_log_q must be a contiguous 1-D tensor of "
+                               f"{num_items} entries, got {tuple(q.shape)}")
+    if q.device != device:
+        raise engine.LgcnError(f"inbatch_step: item_log_q on {q.device}, adjacency on {device}")
+
+
+def inbatch_step(model, adj, users, pos, lambda_reg, temperature=1.0, *, positives=None,
+                 item_log_q=None, check_indices=False):
+    """The in-batch softmax loss of one batch as a tensor whose `.backward()` leaves the
+    parameter `.grad`s of the gathered route (model(adj), fu[users], fi[pos], the same of the
+    layer-0 tables, loss.inbatch_loss_reg with loss.inbatch_off_mask, backward), bit for bit:
+
+        optimizer.zero_grad()
+        loss = model.inbatch_step(adj, users, pos, weight_decay, 0.2, positives=sampler)
+        loss.backward(); optimizer.step()
+
+    Sample b's negatives are the positives of the other samples of its batch: B - 1 negatives per
+    sample and no drawn one, so the step reads, differentiates and scatters 2B rows where the
+    plain step has 3B and negatives="softmax" (2 + M)B. loss.inbatch_loss_torch states the
+    expression: logits <fu[users[b]], fi[pos[c]]> / temperature - item_log_q[pos[c]], one softmax
+    per row, plus the L2 term over the 2B layer-0 rows; both means divide by B. One propagation,
+    then lgcn_inbatch_loss_indexed on views of its output: the [B, B] logits are never stored.
+
+    A column c is dropped from row b (c != b) when it is no true negative of users[b]: the same
+    item again, the same user again, or — positives given: a sampler.BprSampler, or its
+    `positives()` pair (rowptr, items) of int32 tensors on the adjacency's device — pos[c] in the
+    known positives of users[b]. A row left with no column but its own contributes a zero
+    softmax term and keeps its regulariser term. item_log_q (sampler.item_log_q(): float32
+    [num_items] on the adjacency's device) is the logQ correction of the logits.
+
+    users / pos: 1-D contiguous int64 tensors of one length in [1, 32768] on the adjacency's
+    device; the embedding width at most 256. A wrong dtype, device, rank or length of any tensor
+    raises LgcnError before any launch, a temperature that is no finite number > 0 ValueError.
+    check_indices=True validates users and pos against the table sizes with torch ops first (one
+    sync); by default a sample with an index outside its table is skipped: nothing of it is
+    read, it is no column of any row, its terms and gradient rows are zero. On a CPU adjacency
+    the torch expression runs and an index out of range raises LgcnError."""
+    temperature = _check_temperature(temperature, "inbatch_step")
+    dev = adj.device
+    _check_inbatch_tensors(users, pos, dev)
+    U, I = model.num_users, model.num_items
+    pair = None if positives is None else _check_positives(positives, U, dev)
+    if item_log_q is not None:
+        _check_item_log_q(item_log_q, I, dev)
+    d = getattr(model, "embedding_dim", None)
+    if dev.type == "cuda" and d is not None and not 1 <= int(d) <= engine.INBATCH_MAX_D:
+        raise engine.LgcnError(f"inbatch_step: embedding width {d} (1 to {engine.INBATCH_MAX_D})")
+    if check_indices or dev.type != "cuda":
+        for name, t, n in (("users", users, U), ("pos", pos, I)):
+            if bool(((t < 0) | (t >= n)).any()):
+                raise engine.LgcnError(f"inbatch_step: {name} holds an index outside [0, {n})")
+    if dev.type != "cuda":
+        fu, fi, _, u0, i0 = model(adj)
+        return inbatch_loss_torch(fu[users], fi[pos], u0[users], i0[pos], lambda_reg, temperature,
+                                  off=inbatch_off_mask(users, pos, pair),
+                                  q=None if item_log_q is None else item_log_q[pos])
+    n_e0 = model._bpr_n_e0
+    if n_e0 == 2:
+        tensors = [model.user_embedding.weight, model.item_embedding.weight,
+                   model.brand_embedding.weight]
+    else:
+        tensors = [model.user_embedding.weight, model.fused_item_embedding(),
+                   model.brand_embedding.weight, model.item_id_embedding.weight]
+    graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
+    rowptr, items = pair if pair is not None else (None, None)
+    return InBatchStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
+                                     float(lambda_reg), temperature, users, pos, rowptr, items,
+                                     item_log_q, n_e0, *tensors)
+
+
 def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
               item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
-              temperature=1.0):
+              temperature=1.0, *, mask_positives=False, log_q=False):
     """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
     epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
     batch
@@ -693,9 +915,39 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     n_neg (None = the epoch above; an integer in [1, 64]) is passed to sampler.epoch: the draw
     holds n_neg candidate negatives per sample and every batch's neg is [batch, n_neg]; negatives
     ("hardest", "all" or "softmax") is bpr_step's and says what the step does with them;
-    temperature is the softmax step's."""
+    temperature is the softmax step's.
+
+    negatives="in_batch" (with n_neg=None; an integer n_neg raises ValueError): every batch runs
+    model.inbatch_step(adj, users, pos, lambda_reg, temperature) — the in-batch softmax, a
+    sample's negatives being the other samples' positives; the draw's neg column is not used (a
+    neg = -1 is therefore no obstacle on a CPU adjacency). mask_positives=True passes the
+    sampler's own positive lists as `positives`, log_q=True sampler.item_log_q() as `item_log_q`;
+    either with another `negatives` raises ValueError. item_brand with a non-zero weight raises
+    LgcnError, as "softmax" does: the brand term has no softmax form here."""
     if sampler.device != adj.device:
         raise engine.LgcnError(f"bpr_epoch: sampler on {sampler.device}, adjacency on {adj.device}")
+    in_batch = negatives == "in_batch"
+    if (mask_positives or log_q) and not in_batch:
+        raise ValueError("bpr_epoch: mask_positives and log_q belong to negatives='in_batch'")
+    if in_batch:
+        if n_neg is not None:
+            raise ValueError("bpr_epoch: negatives='in_batch' draws no negatives (n_neg must be "
+                             f"None, got {n_neg!r})")
+        temperature = _check_temperature(temperature, "bpr_epoch")
+        if item_brand is not None and brand_loss_weight != 0:
+            raise engine.LgcnError("bpr_epoch: negatives='in_batch' has no brand term")
+        extra = {"positives": sampler if mask_positives else None,
+                 "item_log_q": sampler.item_log_q() if log_q else None}
+        losses = []
+        for users, pos, _ in sampler.epoch(epoch, batch_size, shuffle=shuffle):
+            optimizer.zero_grad()
+            loss = model.inbatch_step(adj, users, pos, lambda_reg, temperature, **extra)
+            loss.backward()
+            optimizer.step()
+            losses.append(loss.detach())
+        if not losses:
+            return torch.empty(0, dtype=torch.float32, device=adj.device)
+        return torch.stack(losses)
     if n_neg is not None and negatives not in ("hardest", "all", "softmax"):
         raise ValueError(f"bpr_epoch: negatives={negatives!r} ('hardest', 'all' or 'softmax')")
     if n_neg is not None and negatives == "softmax":

@@ -64,8 +64,9 @@ extern "C" {
  * (lgcn_score_topk_wide, lgcn_topk_wide_splits, its scratch query, LGCN_TOPK_WIDE_MAX_K) and
  * several negatives per sample (lgcn_bpr_sample_multi, lgcn_bpr_select_hardest,
  * LGCN_BPR_MAX_NEG) and the sampled-softmax loss over them (lgcn_ssm_loss,
- * lgcn_ssm_loss_indexed, lgcn_ssm_keys) were added without a bump: purely additive, no existing
- * symbol, struct or constant changed. */
+ * lgcn_ssm_loss_indexed, lgcn_ssm_keys) and the in-batch softmax loss (lgcn_inbatch_loss,
+ * lgcn_inbatch_loss_indexed, lgcn_inbatch_keys, LGCN_INBATCH_MAX_B / _D / _COEF_B) were added
+ * without a bump: purely additive, no existing symbol, struct or constant changed. */
 #define LGCN_ABI_VERSION 14
 
 /* engine error codes (negative; positive values are hipError_t) */
@@ -945,6 +946,94 @@ int lgcn_ssm_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64
  * [1, LGCN_BPR_MAX_NEG], (2+M) * B past int32. */
 int lgcn_ssm_keys(const int64_t* users, const int64_t* pos, const int64_t* cand, int32_t B,
                   int32_t M, int64_t n_users, int64_t n_items, int64_t* keys, void* stream);
+
+/* ---- in-batch softmax loss: a sample's negatives are the other samples' positives ------------ */
+/* One softmax per sample b over the positives of all B samples of the batch, temperature tau > 0,
+ * an optional per-column correction q (logQ: the log of an item's share of the interactions), plus
+ * lgcn_bpr_loss's L2 term over the sample's two layer-0 rows:
+ *   z_bc = <u_b, p_c> / tau - q_c                                   (q = 0 when NULL)
+ *   on(b,c) = b and c both valid, and (c == b or not off(b,c))
+ *   L_b = log(sum_{c on} exp(z_bc - zmax_b)) + (zmax_b - z_bb)
+ *   *loss = mean_b L_b + lambda * (|U0|^2 + |P0|^2) / B
+ *   g_bc = (softmax_bc - [c == b]) * fp32(fp32(1/tau) / B),  +0 where not on
+ *   du_b = sum_c g_bc p_c,  dp_c = sum_b g_bc u_b,  d(row0) = fp32(fp32(2 * lambda) / B) * row0
+ * Rows: u, p, u0, p0 [B x d] (leading dims ld*). off (NULL = none): uint8 [B x B], off[b * B + c]
+ * != 0 drops column c from row b (c != b; the diagonal is not looked at). valid (NULL = every
+ * sample): uint8 [B]; a sample with valid == 0 is skipped: no row of it is read, it is off as a
+ * column of every row, its L_b, squared norms, gradient rows and coefficients are +0. Both means
+ * divide by B whatever was skipped. A row with no column on besides its own has L_b = 0 and zero
+ * coefficients and keeps its regulariser term. q: float [B], q[c] the correction of column c; it
+ * enters the logits only.
+ * The B x B logits are never stored: 32 x 32 score tiles are recomputed by each sweep on
+ * v_mfma_f32_32x32x2_f32 (exact f32, bitwise an fmaf chain). Orders, all fp32:
+ *  - a score <u_b, p_c>: one fmaf chain from +0 over the features in the order 0, 4, 1, 5, 2, 6,
+ *    3, 7, then 8, 12, 9, 13, ... (MFMA step 4q + x adds feature 8q + x, then 8q + 4 + x), over
+ *    ceil(d / 32) * 32 features, those past d - 1 being +0 products (exact). It depends on the two
+ *    rows and d alone, not on B or on where the pair sits; z = fp32(fp32(score * it) - q_c),
+ *    it = fp32(1 / tau);
+ *  - zmax_b: the maximum over the columns on (exact in any order);
+ *  - Z_b: a block of four waves owns users [32 i, 32 i + 32); wave w takes column tiles t = w,
+ *    w + 4, ... (columns [32 t, 32 t + 32)) in ascending t. Per wave, lane half h of a user sums
+ *    expf(z - zmax) over the columns on of its tiles in ascending t and, inside a tile, over the
+ *    local columns (r & 3) + 8 * (r >> 2) + 4 * h in ascending r = 0..15, one add each from +0;
+ *    then half 0 + half 1; then the waves ((w0 + w1) + w2) + w3;
+ *    L_b = fp32(logf(Z_b) + fp32(zmax_b - z_bb));
+ *  - g_bc = fp32(fp32(fp32(expf(z_bc - zmax_b) / Z_b) - [c == b]) * cf), cf = fp32(it / B): one
+ *    device function, evaluated by both gradient sweeps on the same score bits;
+ *  - du_b[k] (column-tile order) and dp_c[k] (row-tile order): a block of four waves owns 32
+ *    output rows; wave w takes the other side's tiles t = w, w + 4, ... in ascending t and keeps
+ *    one fmaf chain per output element from +0: per tile 16 MFMA steps r = 0..15, step r adding
+ *    the other side's local sample (r & 3) + 8 * (r >> 2), then that + 4 (g * row[k], +0 where not
+ *    on or past B); then the waves ((w0 + w1) + w2) + w3;
+ *  - squared norms: per lane one fmaf chain from +0 over k = lane, lane + 64, ... of u0[k]^2 then
+ *    p0[k]^2, then the 32, 16, ..., 1 xor butterfly;
+ *  - *loss = fp32(sl / B) + fp32(fp32(lambda * sr) / B), sl / sr the sums of L_b / of the squared
+ *    norms in lgcn_bpr_loss's fixed batch order (256 strided partial sums, then a halving tree).
+ * No float atomics: run-to-run identical.
+ * grads = [2 x 2B x d]: half 0 the layer-0 gradient rows, half 1 the final ones; inside a half
+ * rows [0, B) users, [B, 2B) positives: one permutation of lgcn_inbatch_keys' 2B keys indexes
+ * either half as lgcn_rows_scatter's source. work: scratch, float [5 x B] (L_b, squared norms,
+ * zmax_b, Z_b, q per column). mask: scratch, uint32 [B x ceil(B / 32)] (the on bits, formed once
+ * per batch). coef (NULL = not wanted): [B x B], g_bc; for tests, refused for B >
+ * LGCN_INBATCH_MAX_COEF_B. Allocates nothing, never synchronises, everything runs on `stream`.
+ * LGCN_EINVAL before any launch: a NULL pointer other than off / valid / q / coef / stream, B
+ * outside [1, LGCN_INBATCH_MAX_B], d outside [1, LGCN_INBATCH_MAX_D], ld < d, tau not finite or
+ * <= 0. */
+#define LGCN_INBATCH_MAX_B      32768
+#define LGCN_INBATCH_MAX_D      256
+#define LGCN_INBATCH_MAX_COEF_B 4096
+int lgcn_inbatch_loss(const float* u, int64_t ldu, const float* p, int64_t ldp, const float* u0,
+                      int64_t ldu0, const float* p0, int64_t ldp0, const uint8_t* off,
+                      const uint8_t* valid, const float* q, int32_t B, int32_t d, float lambda,
+                      float temperature, float* work, uint32_t* mask, float* loss, float* grads,
+                      float* coef, void* stream);
+
+/* lgcn_inbatch_loss with the rows read from the tables (lgcn_bpr_loss_indexed's four) by users /
+ * pos, int64 [B], and the masks derived on the device. A sample whose user or positive lies
+ * outside its table is skipped (valid == 0) and nothing of it is dereferenced. For two valid
+ * samples off(b,c) holds when pos[c] == pos[b] (the same item again), or users[c] == users[b]
+ * (pos[c] is a known positive of that user), or — pos_rowptr / pos_items given: lgcn_bpr_sample's
+ * CSR, int32, [n_users + 1] and the sorted, de-duplicated lists; both NULL = no lists — pos[c] is
+ * in the list of users[b] (a binary search). item_q (NULL = none): float [n_items], q_c =
+ * item_q[pos[c]]. The same kernel bodies: bitwise lgcn_inbatch_loss's outputs on gathered copies
+ * with the matching off / valid / q. Also LGCN_EINVAL: n_users or n_items < 0, one of pos_rowptr /
+ * pos_items NULL and the other not. */
+int lgcn_inbatch_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                              const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                              int64_t n_users, int64_t n_items, const int64_t* users,
+                              const int64_t* pos, const int32_t* pos_rowptr,
+                              const int32_t* pos_items, const float* item_q, int32_t B, int32_t d,
+                              float lambda, float temperature, float* work, uint32_t* mask,
+                              float* loss, float* grads, float* coef, void* stream);
+
+/* The 2B destination keys of that batch's gradient rows, keys int64 [2 x B] in grads' row order,
+ * lgcn_bpr_keys' numbering: 2 * users[b], then 2 * (n_users + pos[b]) (bit 0 clear: an item row is
+ * summed as one run in ascending b, autograd's index_put order for the gather index pos). Both
+ * keys of a skipped sample are "none" = 2 * (n_users + n_items); sort with n_keys = none + 1.
+ * LGCN_EINVAL: a NULL pointer other than stream, B outside [1, LGCN_INBATCH_MAX_B], n_users or
+ * n_items < 0, n_users + n_items > 0x3ffffffe (the sort's int32 keys). */
+int lgcn_inbatch_keys(const int64_t* users, const int64_t* pos, int32_t B, int64_t n_users,
+                      int64_t n_items, int64_t* keys, void* stream);
 
 /* ---- LightGCN_Fusion item pre-layer (models/lightgcn_fusion.py:45-49) ------------------------ */
 /* out[i,:] = leaky_relu(weight · [id_emb[i,:] | content[i,:]] + bias, slope) for i < n_items,

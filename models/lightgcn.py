@@ -125,18 +125,30 @@ class LightGCN(nn.Module):
                               brand_loss_weight=brand_loss_weight, negatives=negatives,
                               return_negatives=return_negatives, temperature=temperature)
 
+    def inbatch_step(self, adj, users, pos, lambda_reg, temperature=1.0, *, positives=None,
+                     item_log_q=None, check_indices=False):
+        """The in-batch softmax + L2 loss of one batch in one call that keeps the batch indices
+        (train.inbatch_step): a sample's negatives are the other samples' positives, no drawn
+        negatives; `positives` (a BprSampler or its (rowptr, items)) drops a user's known
+        positives from its negatives, `item_log_q` is the logQ correction."""
+        return train.inbatch_step(self, adj, users, pos, lambda_reg, temperature,
+                                  positives=positives, item_log_q=item_log_q,
+                                  check_indices=check_indices)
+
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
                   item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
-                  temperature=1.0):
+                  temperature=1.0, *, mask_positives=False, log_q=False):
         """One epoch of bpr_step batches over one device-side draw of the sampler
         (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
         `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
         engine, with torch.optim.Adam's bits. n_neg = M draws M candidate negatives per sample
-        for bpr_step's `negatives` mode."""
+        for bpr_step's `negatives` mode; negatives="in_batch" (n_neg=None) runs inbatch_step on
+        every batch, with mask_positives / log_q taken from the sampler."""
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
                                brand_loss_weight=brand_loss_weight, n_neg=n_neg,
-                               negatives=negatives, temperature=temperature)
+                               negatives=negatives, temperature=temperature,
+                               mask_positives=mask_positives, log_q=log_q)
 
     def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
         """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass
