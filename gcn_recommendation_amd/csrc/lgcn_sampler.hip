@@ -1,7 +1,8 @@
 // lgcn_sampler.hip — the BPR negative sampler (main.py:349-363, BPRDataset.__getitem__) on the
 // device: lgcn_bpr_sample writes the (user, positive, negative) triples of a run of interactions,
 // a whole epoch in one launch; lgcn_bpr_sample_multi writes n_neg negatives per triple (ordinal m
-// = the same draw with counter word 3 = m). Declared in include/lgcn.h, which defines the draw.
+// = the same draw with counter word 3 = m); lgcn_bpr_sample_weighted draws them in proportion to
+// integer item weights. Declared in include/lgcn.h, which defines the draws.
 //
 // The negative of interaction idx is a pure function of (seed, epoch, idx, the user's positive
 // list, n_items): 64 Philox4x32-10 bits -> j = mulhi64(r64, n_free) -> the j-th item missing from
@@ -136,6 +137,85 @@ __global__ __launch_bounds__(kBlock) void k_bpr_sample_multi(
     }
 }
 
+// One ordinal's weighted draw (include/lgcn.h, lgcn_bpr_sample_weighted): r = mulhi64(r64, w_free)
+// is a position in the concatenated weights of the user's free items; t* = the number of list
+// positions whose item starts at or before it (item_cumw[L[t]] - pw[t], the free weight below
+// L[t], is non-decreasing in t); r + pw[t*] is the same position in the weights of all items, and
+// the item that covers it is an upper-bound search over item_cumw [n_items + 1]. pcw = pos_cumw +
+// beg. An L[mid] outside [0, n_items) is not used as an index; a result outside it is -1.
+__device__ __forceinline__ int64_t draw_weighted(int64_t idx, uint32_t epoch, uint32_t ordinal,
+                                                 uint32_t seed_lo, uint32_t seed_hi,
+                                                 int64_t w_free, const int32_t* __restrict__ L,
+                                                 const int64_t* __restrict__ pcw, int32_t deg,
+                                                 const int64_t* __restrict__ item_cumw,
+                                                 int32_t n_items) {
+    uint32_t r0, r1;
+    philox4x32_10((uint32_t)idx, (uint32_t)((uint64_t)idx >> 32), epoch, ordinal, seed_lo, seed_hi,
+                  r0, r1);
+    const uint64_t r64 = ((uint64_t)r1 << 32) | r0;
+    const int64_t r = (int64_t)__umul64hi(r64, (uint64_t)w_free);
+    const int64_t base = pcw[0];
+    int32_t lo = 0, hi = deg;  // t* = the first t with item_cumw[L[t]] - pw[t] > r
+    while (lo < hi) {
+        const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
+        const int32_t l = L[mid];
+        if ((uint32_t)l < (uint32_t)n_items && item_cumw[l] - (pcw[mid] - base) <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    const int64_t rr = r + (pcw[lo] - base);
+    int32_t a = 0, b = n_items + 1;  // the first k in [0, n_items] with item_cumw[k] > rr
+    while (a < b) {
+        const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
+        if (item_cumw[mid] <= rr) a = mid + 1;
+        else b = mid;
+    }
+    const int32_t neg = a - 1;
+    return neg >= 0 && neg < n_items ? (int64_t)neg : -1;
+}
+
+// k_bpr_sample_multi with the weighted draw: the slot's user, beg, deg and w_free are loaded once
+// and reused for all n_neg ordinals.
+__global__ __launch_bounds__(kBlock) void k_bpr_sample_weighted(
+    const int32_t* __restrict__ inter_user, const int32_t* __restrict__ inter_item,
+    int64_t n_inter, const int64_t* __restrict__ order, int64_t first, int64_t count,
+    const int32_t* __restrict__ pos_rowptr, const int32_t* __restrict__ pos_items,
+    const int64_t* __restrict__ pos_cumw, const int64_t* __restrict__ item_cumw, int32_t n_users,
+    int32_t n_items, uint32_t seed_lo, uint32_t seed_hi, uint32_t epoch, int32_t n_neg,
+    int64_t* __restrict__ users, int64_t* __restrict__ pos, int64_t* __restrict__ neg,
+    int32_t* __restrict__ n_unsampled) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t W = item_cumw[n_items];
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < count; s += stride) {
+        const int64_t idx = order != nullptr ? order[first + s] : first + s;
+        int64_t ou = -1, op = -1;
+        int32_t beg = 0, deg = 0;
+        int64_t w_free = 0;  // stays 0: every ordinal of the slot is -1
+        if (idx >= 0 && idx < n_inter) {
+            const int32_t u = inter_user[idx];
+            if (u >= 0 && u < n_users) {
+                ou = u;
+                op = inter_item[idx];
+                beg = pos_rowptr[u];
+                deg = pos_rowptr[u + 1] - beg;
+                if (beg >= 0 && deg >= 0)
+                    w_free = W - (pos_cumw[(int64_t)beg + deg] - pos_cumw[beg]);
+                if (w_free <= 0) {  // also: not a row of a CSR
+                    w_free = 0;
+                    if (n_unsampled != nullptr) atomicAdd(n_unsampled, 1);  // once per slot
+                }
+            }
+        }
+        users[s] = ou;
+        pos[s] = op;
+        int64_t* __restrict__ out = neg + s * n_neg;
+        for (int32_t m = 0; m < n_neg; ++m)
+            out[m] = w_free > 0 ? draw_weighted(idx, epoch, (uint32_t)m, seed_lo, seed_hi, w_free,
+                                                pos_items + beg, pos_cumw + beg, deg, item_cumw,
+                                                n_items)
+                                : -1;
+    }
+}
+
 // CUs of the current device: lgcn_device_info, asked once per device and kept (the launch path
 // then costs one hipGetDevice). A failed query is returned, not papered over.
 int cu_count(int* n_cu) {
@@ -215,6 +295,33 @@ int lgcn_bpr_sample_multi(const int32_t* inter_user, const int32_t* inter_item, 
                        order, first, count, pos_rowptr, pos_items, (int32_t)n_users,
                        (int32_t)n_items, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, n_neg,
                        users, pos, neg, n_unsampled);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lgcn_bpr_sample_weighted(const int32_t* inter_user, const int32_t* inter_item,
+                             int64_t n_inter, const int64_t* order, int64_t first, int64_t count,
+                             const int32_t* pos_rowptr, const int32_t* pos_items,
+                             const int64_t* pos_cumw, const int64_t* item_cumw, int64_t n_users,
+                             int64_t n_items, uint64_t seed, uint32_t epoch, int32_t n_neg,
+                             int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_unsampled,
+                             void* stream) {
+    constexpr int64_t kLimit = (int64_t)1 << 31;
+    if (n_inter < 0 || n_users < 0 || n_items < 0) return LGCN_EINVAL;
+    if (n_inter >= kLimit || n_users >= kLimit || n_items >= kLimit) return LGCN_EINVAL;
+    if (first < 0 || count < 0 || first > INT64_MAX - count) return LGCN_EINVAL;
+    if (n_neg < 1 || n_neg > LGCN_BPR_MAX_NEG || count > INT64_MAX / n_neg) return LGCN_EINVAL;
+    if (count == 0) return 0;
+    if (!inter_user || !inter_item || !pos_rowptr || !pos_items) return LGCN_EINVAL;
+    if (!pos_cumw || !item_cumw) return LGCN_EINVAL;
+    if (!users || !pos || !neg) return LGCN_EINVAL;
+    int64_t blocks = 0;
+    if (const int rc = sample_blocks(count, &blocks)) return rc;
+    hipLaunchKernelGGL(k_bpr_sample_weighted, dim3((uint32_t)blocks), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), inter_user, inter_item, n_inter,
+                       order, first, count, pos_rowptr, pos_items, pos_cumw, item_cumw,
+                       (int32_t)n_users, (int32_t)n_items, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       epoch, n_neg, users, pos, neg, n_unsampled);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -3,6 +3,8 @@
 // temperature, plus the L2 term of the layer-0 rows, and every input gradient.
 //   lgcn_ssm_loss          the rows given as gathered blocks
 //   lgcn_ssm_loss_indexed  the rows read from the tables by index (the fused step)
+//   lgcn_ssm_loss_q, lgcn_ssm_loss_indexed_q  the two with a logQ correction of the logits; the
+//                          two above are these with q = NULL
 //   lgcn_ssm_keys          the (2+M)B destination keys of the batch's per-sample gradient rows
 // Declared in include/lgcn.h; the kernels are in lgcn_ssm_rows.h. The sort, the scatter and the
 // clear of the step are the BPR step's (lgcn_coo_sort_perm, lgcn_rows_scatter, lgcn_rows_clear).
@@ -58,12 +60,22 @@ int lgcn_ssm_loss(const float* u, int64_t ldu, const float* p, int64_t ldp, cons
                   const float* n0, int64_t ldn0, const uint8_t* valid, int32_t B, int32_t M,
                   int32_t d, float lambda, float temperature, float* terms, float* loss,
                   float* grads, float* coef, void* stream) {
+    return lgcn_ssm_loss_q(u, ldu, p, ldp, n, ldn, u0, ldu0, p0, ldp0, n0, ldn0, valid, nullptr,
+                           nullptr, B, M, d, lambda, temperature, terms, loss, grads, coef, stream);
+}
+
+int lgcn_ssm_loss_q(const float* u, int64_t ldu, const float* p, int64_t ldp, const float* n,
+                    int64_t ldn, const float* u0, int64_t ldu0, const float* p0, int64_t ldp0,
+                    const float* n0, int64_t ldn0, const uint8_t* valid, const float* q_pos,
+                    const float* q_neg, int32_t B, int32_t M, int32_t d, float lambda,
+                    float temperature, float* terms, float* loss, float* grads, float* coef,
+                    void* stream) {
     if (!sizes_ok(B, M, d) || !tau_ok(temperature) || !loss || !terms || !grads)
         return LGCN_EINVAL;
     if (!u || !p || !n || !u0 || !p0 || !n0) return LGCN_EINVAL;
     if (ldu < d || ldp < d || ldn < d || ldu0 < d || ldp0 < d || ldn0 < d) return LGCN_EINVAL;
     const lgcn_ssm::GatheredRows rows = {{u, p, u0, p0}, {ldu, ldp, ldu0, ldp0}, n, ldn,
-                                         n0, ldn0, valid};
+                                         n0, ldn0, valid, q_pos, q_neg};
     return lgcn_ssm::launch(rows, B, M, d, lambda, temperature, terms, loss, grads, coef,
                             reinterpret_cast<hipStream_t>(stream));
 }
@@ -74,13 +86,24 @@ int lgcn_ssm_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64
                           const int64_t* pos, const int64_t* cand, int32_t B, int32_t M,
                           int32_t d, float lambda, float temperature, float* terms, float* loss,
                           float* grads, float* coef, void* stream) {
+    return lgcn_ssm_loss_indexed_q(fu, ld_fu, fi, ld_fi, u0, ld_u0, i0, ld_i0, n_users, n_items,
+                                   users, pos, cand, nullptr, B, M, d, lambda, temperature, terms,
+                                   loss, grads, coef, stream);
+}
+
+int lgcn_ssm_loss_indexed_q(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                            const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                            int64_t n_users, int64_t n_items, const int64_t* users,
+                            const int64_t* pos, const int64_t* cand, const float* item_q,
+                            int32_t B, int32_t M, int32_t d, float lambda, float temperature,
+                            float* terms, float* loss, float* grads, float* coef, void* stream) {
     if (!sizes_ok(B, M, d) || !tau_ok(temperature) || !loss || !terms || !grads)
         return LGCN_EINVAL;
     if (!fu || !fi || !u0 || !i0 || !users || !pos || !cand) return LGCN_EINVAL;
     if (ld_fu < d || ld_fi < d || ld_u0 < d || ld_i0 < d) return LGCN_EINVAL;
     if (n_users < 0 || n_items < 0) return LGCN_EINVAL;
     const lgcn_ssm::IndexedRows rows = {{fu, fi, u0, i0}, {ld_fu, ld_fi, ld_u0, ld_i0},
-                                        users, pos, cand, n_users, n_items};
+                                        users, pos, cand, n_users, n_items, item_q};
     return lgcn_ssm::launch(rows, B, M, d, lambda, temperature, terms, loss, grads, coef,
                             reinterpret_cast<hipStream_t>(stream));
 }

@@ -3,7 +3,8 @@
 // two are bitwise equal by construction), and the fixed-order batch reduction. A sample has
 // 2 + M rows in each of the two tables' views: user, positive, M candidate negatives.
 //
-//   z_0 = <u,p> / tau, z_m = <u,n_m> / tau          (scores: lgcn_bpr::row_scores)
+//   z_0 = <u,p> / tau - q_0, z_m = <u,n_m> / tau - q_m   (scores: lgcn_bpr::row_scores; q: the
+//                                                         optional logQ correction, else no term)
 //   L_b = log(sum_j exp(z_j - z_max)) + (z_max - z_0)
 //   loss = mean_b L_b + lambda * (|U0|^2 + |P0|^2 + |N0|^2) / B
 //
@@ -32,7 +33,7 @@ struct SampleRows {
 };
 
 // rows of gathered blocks: sample b is row b of u, p, u0, p0 and rows b * M + m of the two
-// [B*M x d] candidate blocks; valid (NULL = every entry) masks candidates
+// [B*M x d] candidate blocks; valid (NULL = every entry) masks candidates; q likewise by ordinal
 struct GatheredRows {
     const float* p[4];  // u, p, u0, p0
     int64_t ld[4];
@@ -41,10 +42,20 @@ struct GatheredRows {
     const float* n0;
     int64_t ldn0;
     const uint8_t* valid;
+    const float* q_pos;  // [B], nullptr = none
+    const float* q_neg;  // [B x M], nullptr = none
     __device__ __forceinline__ bool get(int64_t b, SampleRows& o) const {
 #pragma unroll
         for (int i = 0; i < 4; ++i) o.r[i] = p[i] + b * ld[i];
         return true;
+    }
+    // the logQ correction: whether there is one, the positive's, the candidate's at ordinal `at`
+    __device__ __forceinline__ bool has_q() const { return q_pos != nullptr || q_neg != nullptr; }
+    __device__ __forceinline__ float qpos(int64_t b) const {
+        return q_pos != nullptr ? q_pos[b] : 0.f;
+    }
+    __device__ __forceinline__ float qcand(int64_t at) const {
+        return q_neg != nullptr ? q_neg[at] : 0.f;
     }
     // candidate m of sample b: its row ordinal, and whether it takes part
     __device__ __forceinline__ bool cand(int64_t b, int m, int32_t M, int64_t& at) const {
@@ -57,7 +68,7 @@ struct GatheredRows {
 
 // rows of the tables themselves: tab = final user, final item, layer-0 user, layer-0 item. A
 // sample whose user or positive lies outside its table has no rows (false); a candidate outside
-// [0, n_items) takes no part; nothing of either is dereferenced.
+// [0, n_items) takes no part; nothing of either is dereferenced. q is item_q at the item's index.
 struct IndexedRows {
     const float* tab[4];
     int64_t ld[4];
@@ -65,6 +76,7 @@ struct IndexedRows {
     const int64_t* pos;
     const int64_t* neg;  // [B x M]
     int64_t n_users, n_items;
+    const float* item_q;  // [n_items], nullptr = none
     __device__ __forceinline__ bool get(int64_t b, SampleRows& o) const {
         const int64_t iu = users[b], ip = pos[b];
         if (iu < 0 || iu >= n_users || ip < 0 || ip >= n_items) return false;
@@ -74,6 +86,10 @@ struct IndexedRows {
         o.r[3] = tab[3] + ip * ld[3];
         return true;
     }
+    // asked only of a sample that has rows and of a candidate that takes part: both in range
+    __device__ __forceinline__ bool has_q() const { return item_q != nullptr; }
+    __device__ __forceinline__ float qpos(int64_t b) const { return item_q[pos[b]]; }
+    __device__ __forceinline__ float qcand(int64_t at) const { return item_q[at]; }
     __device__ __forceinline__ bool cand(int64_t b, int m, int32_t M, int64_t& at) const {
         at = neg[b * M + m];
         return at >= 0 && at < n_items;
@@ -111,6 +127,8 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_ssm_rows(
     int64_t at = -1;
     const bool ok = have && lane < M && rows.cand(b, lane, M, at);
     const uint64_t live = __ballot(ok);
+    const bool has_q = rows.has_q();                            // uniform over the grid
+    const float qm = has_q && ok ? rows.qcand(at) : 0.f;        // lane m: q of candidate m
     if (live == 0) {  // skipped: +0 rows, zero terms and coefficients
         for (int k = lane; k < d; k += kWave) gu[k] = gp[k] = gu0[k] = gp0[k] = 0.f;
         for (int64_t o = lane; o < (int64_t)M * d; o += kWave) gn[o] = gn0[o] = 0.f;
@@ -135,7 +153,8 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_ssm_rows(
     const float* const pr[1] = {pb};
     float s0[1];
     row_scores(ub, pr, d, lane, s0);
-    const float z0 = s0[0] * inv_tau;
+    float z0 = s0[0] * inv_tau;
+    if (has_q) z0 = z0 - rows.qpos(b);
     float z = 0.f;  // lane m: z_m
     uint64_t todo = live;
     while (todo != 0) {
@@ -167,6 +186,7 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_ssm_rows(
             }
         }
     }
+    if (has_q) z = z - qm;
     sq = wave_sum(sq);
     const float zmax = fmaxf(z0, wave_max(ok ? z : z0));
     const float e0 = expf(z0 - zmax);

@@ -233,6 +233,9 @@ ABI = [
     ("lgcn_bpr_sample_multi", ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64,
                                              ctypes.c_uint64, ctypes.c_uint32, _I32, _P, _P, _P,
                                              _P, _P]),
+    ("lgcn_bpr_sample_weighted", ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _I64,
+                                                _I64, ctypes.c_uint64, ctypes.c_uint32, _I32, _P,
+                                                _P, _P, _P, _P]),
     ("lgcn_bpr_select_hardest", ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _I32, _I32,
                                                _I32, _P, _P, _P]),
     ("lgcn_ssm_loss", ctypes.c_int, [_P, _I64] * 6 + [_P, _I32, _I32, _I32, ctypes.c_float,
@@ -240,6 +243,13 @@ ABI = [
     ("lgcn_ssm_loss_indexed", ctypes.c_int, [_P, _I64] * 4 + [_I64, _I64, _P, _P, _P, _I32, _I32,
                                                               _I32, ctypes.c_float, ctypes.c_float,
                                                               _P, _P, _P, _P, _P]),
+    ("lgcn_ssm_loss_q", ctypes.c_int, [_P, _I64] * 6 + [_P, _P, _P, _I32, _I32, _I32,
+                                                        ctypes.c_float, ctypes.c_float, _P, _P, _P,
+                                                        _P, _P]),
+    ("lgcn_ssm_loss_indexed_q", ctypes.c_int, [_P, _I64] * 4 + [_I64, _I64, _P, _P, _P, _P, _I32,
+                                                                _I32, _I32, ctypes.c_float,
+                                                                ctypes.c_float, _P, _P, _P, _P,
+                                                                _P]),
     ("lgcn_ssm_keys", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I64, _I64, _P, _P]),
     ("lgcn_inbatch_loss", ctypes.c_int, [_P, _I64] * 4 + [_P, _P, _P, _I32, _I32, ctypes.c_float,
                                                           ctypes.c_float, _P, _P, _P, _P, _P, _P]),

@@ -161,10 +161,12 @@ def bpr_brand_loss_reg(final_user_emb, final_pos_item_emb, final_neg_item_emb,
 class SSMLossFunction(torch.autograd.Function):
     """BPRLossFunction's sibling for the sampled-softmax loss (lgcn_ssm_loss): (u, p, n, u0, p0,
     n0, valid, lambda, temperature) with n / n0 the [B, M, d] candidate blocks and valid a uint8
-    [B, M] mask or None; the six gradient blocks come from the same launch."""
+    [B, M] mask or None; the six gradient blocks come from the same launch. q_pos (float32 [B])
+    and q_neg (float32 [B, M]), each or None: the logQ correction (lgcn_ssm_loss_q)."""
 
     @staticmethod
-    def forward(ctx, u, p, n, u0, p0, n0, valid, lambda_reg, temperature):
+    def forward(ctx, u, p, n, u0, p0, n0, valid, lambda_reg, temperature, q_pos=None,
+                q_neg=None):
         lib = engine.load_library()
         B, d = u.shape
         if n.dim() != 3 or int(n.shape[0]) != B or not 1 <= int(n.shape[1]) <= engine.BPR_MAX_NEG:
@@ -186,6 +188,12 @@ class SSMLossFunction(torch.autograd.Function):
         if valid is not None and (valid.shape != (B, M) or valid.dtype != torch.uint8 or
                                   valid.device != dev or not valid.is_contiguous()):
             raise engine.LgcnError("ssm_loss: valid must be a contiguous uint8 [B, M] tensor")
+        for name, t, shape in (("q_pos", q_pos, (B,)), ("q_neg", q_neg, (B, M))):
+            if t is not None and (not torch.is_tensor(t) or t.shape != shape or
+                                  t.dtype != torch.float32 or t.device != dev or
+                                  not t.is_contiguous()):
+                raise engine.LgcnError(f"ssm_loss: {name} must be a contiguous float32 tensor of "
+                                       f"shape {shape} on {dev}")
         terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grads = torch.empty((2, (2 + M) * B, d), dtype=torch.float32, device=dev)
@@ -196,10 +204,11 @@ class SSMLossFunction(torch.autograd.Function):
                       (blocks[1], blocks[1].stride(1))):
             args += [engine._ptr(t), ld]
         with torch.cuda.device(dev):
-            engine._check(lib.lgcn_ssm_loss(*args, engine._ptr(valid), B, M, d, float(lambda_reg),
-                                            float(temperature), engine._ptr(terms),
-                                            engine._ptr(loss), engine._ptr(grads), None,
-                                            engine._stream(dev)), "lgcn_ssm_loss")
+            engine._check(lib.lgcn_ssm_loss_q(*args, engine._ptr(valid), engine._ptr(q_pos),
+                                              engine._ptr(q_neg), B, M, d, float(lambda_reg),
+                                              float(temperature), engine._ptr(terms),
+                                              engine._ptr(loss), engine._ptr(grads), None,
+                                              engine._stream(dev)), "lgcn_ssm_loss_q")
         ctx.save_for_backward(grads)
         ctx.dims = (B, M, d)
         return loss
@@ -212,7 +221,7 @@ class SSMLossFunction(torch.autograd.Function):
         out = []
         for half in (1, 0):  # the final rows, then the layer-0 rows
             out += [sg[half, :B], sg[half, B:2 * B], sg[half, 2 * B:].view(B, M, d)]
-        return tuple(out) + (None, None, None)
+        return tuple(out) + (None,) * 5
 
 
 def _check_temperature(temperature, what):
@@ -224,9 +233,10 @@ def _check_temperature(temperature, what):
 
 def ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb, initial_user_emb,
                    initial_pos_item_emb, initial_neg_item_emb, lambda_reg, temperature=1.0,
-                   valid=None):
+                   valid=None, q_pos=None, q_neg=None):
     """The sampled-softmax loss as a torch expression, in the dtype of its inputs: what a CPU
-    adjacency runs, and the reference the HIP kernel is measured against."""
+    adjacency runs, and the reference the HIP kernel is measured against. q_pos [B] / q_neg
+    [B, M], each or None: the logQ correction, subtracted from the logits after the division."""
     u, p, n = final_user_emb, final_pos_item_emb, final_neg_item_emb
     u0, p0, n0 = initial_user_emb, initial_pos_item_emb, initial_neg_item_emb
     pos_scores = torch.sum(u * p, dim=1)
@@ -239,6 +249,16 @@ def ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb, initi
         u0 = u0 * keep.unsqueeze(-1).to(u0.dtype)
         p0 = p0 * keep.unsqueeze(-1).to(p0.dtype)
     logits = torch.cat([pos_scores.unsqueeze(1), neg_scores], dim=1) / temperature
+    if q_pos is not None or q_neg is not None:
+        q = torch.zeros_like(logits)
+        if q_pos is not None:
+            q[:, 0] = q_pos.to(logits.dtype)
+        if q_neg is not None:
+            q[:, 1:] = q_neg.to(logits.dtype)
+        if valid is not None:  # the q of a masked candidate or of a skipped sample is not read
+            q[:, 1:] = q[:, 1:].masked_fill(~on, 0.0)
+            q[:, 0] = q[:, 0].masked_fill(~keep, 0.0)
+        logits = logits - q
     ssm = torch.mean(torch.logsumexp(logits, dim=1) - logits[:, 0])
     reg = lambda_reg * (u0.norm(2).pow(2) + p0.norm(2).pow(2) + n0.norm(2).pow(2)) / float(len(u))
     return ssm + reg
@@ -246,28 +266,31 @@ def ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb, initi
 
 def ssm_loss_reg(final_user_emb, final_pos_item_emb, final_neg_item_emb,
                  initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
-                 lambda_reg, temperature=1.0, valid=None):
+                 lambda_reg, temperature=1.0, valid=None, q_pos=None, q_neg=None):
     """Sampled-softmax (InfoNCE) loss over all M negatives of a sample, plus bpr_loss_reg's L2
     term: bpr_loss_reg's call with [B, M, d] negative blocks.
 
-        z_0 = <u, p> / temperature, z_m = <u, n_m> / temperature
+        z_0 = <u, p> / temperature - q_pos, z_m = <u, n_m> / temperature - q_neg[:, m]
         loss = mean_b (logsumexp_j z_j - z_0) + lambda_reg * (|U0|^2 + |P0|^2 + |N0|^2) / B
 
     valid (None = every entry): a uint8 or bool [B, M] mask; a candidate with valid == 0 is no
     term of the softmax or of the regulariser, a sample without a valid candidate contributes
-    nothing; the means still divide by B. On a HIP device loss and all six input gradients come
+    nothing; the means still divide by B. q_pos (float32 [B]) / q_neg (float32 [B, M]), each or
+    None = no such term: the logQ correction of negatives drawn with probability Q — the log
+    probabilities of the positive and of each candidate (sampler.neg_log_q()[pos] and [neg]); it
+    enters the logits only. On a HIP device loss and all six input gradients come
     from one launch (lgcn_ssm_loss, include/lgcn.h states its orders of summation); on CPU
     tensors ssm_loss_torch runs."""
     temperature = _check_temperature(temperature, "ssm_loss_reg")
     if final_user_emb.device.type != "cuda":
         return ssm_loss_torch(final_user_emb, final_pos_item_emb, final_neg_item_emb,
                               initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
-                              lambda_reg, temperature, valid)
+                              lambda_reg, temperature, valid, q_pos, q_neg)
     if valid is not None and valid.dtype == torch.bool:
         valid = valid.to(torch.uint8)
     return SSMLossFunction.apply(final_user_emb, final_pos_item_emb, final_neg_item_emb,
                                  initial_user_emb, initial_pos_item_emb, initial_neg_item_emb,
-                                 valid, float(lambda_reg), temperature)
+                                 valid, float(lambda_reg), temperature, q_pos, q_neg)
 
 
 # ---- in-batch softmax: a sample's negatives are the other samples' positives --------------------

@@ -406,9 +406,10 @@ class BprBrandStepFunction(torch.autograd.Function):
 
 
 class SsmStepFunction(torch.autograd.Function):
-    """(graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, n_e0, *segments) ->
-    the sampled-softmax loss over all M candidates of cand [B, M] (loss.ssm_loss_reg's
-    expression), segments as BprStepFunction's.
+    """(graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, item_q, n_e0,
+    *segments) -> the sampled-softmax loss over all M candidates of cand [B, M]
+    (loss.ssm_loss_reg's expression), segments as BprStepFunction's; item_q: the float32
+    [items] logQ correction looked up by item index (lgcn_ssm_loss_indexed_q), or None.
 
     BprStepFunction with 2 + M rows per sample: lgcn_ssm_loss_indexed reads them from the output
     buffer and the layer-0 tables and keeps grads = [2 x (2+M)B x d] (layer-0 half, final half,
@@ -416,8 +417,8 @@ class SsmStepFunction(torch.autograd.Function):
     row and a positive row are read, differentiated and scattered once per sample, not M times."""
 
     @staticmethod
-    def forward(ctx, graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, n_e0,
-                *segments):
+    def forward(ctx, graph, K, hub_threshold, lambda_reg, temperature, users, pos, cand, item_q,
+                n_e0, *segments):
         if n_e0 not in (1, 2):
             raise engine.LgcnError(f"bpr_step: n_e0={n_e0} (1 or 2)")
         nseg = len(segments) - (2 - n_e0)
@@ -434,18 +435,20 @@ class SsmStepFunction(torch.autograd.Function):
         if i0.shape != (I, d) or i0.dtype != torch.float32 or i0.device != dev or \
                 (I > 0 and i0.stride(1) != 1):
             raise engine.LgcnError("bpr_step: the item regulariser table must be [items x d] fp32")
+        if item_q is not None:
+            _check_item_log_q(item_q, I, dev, "bpr_step: neg_log_q")
         B, M = int(cand.shape[0]), int(cand.shape[1])
         fu, fi, u0 = out[:U], out[U:U + I], segs[0]
         terms = torch.empty(2 * B, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grads = torch.empty((2, (2 + M) * B, d), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            engine._check(lib.lgcn_ssm_loss_indexed(
+            engine._check(lib.lgcn_ssm_loss_indexed_q(
                 engine._ptr(fu), d, engine._ptr(fi), d, engine._ptr(u0), d, engine._ptr(i0),
                 i0.stride(0) if I else d, U, I, engine._ptr(users), engine._ptr(pos),
-                engine._ptr(cand), B, M, d, float(lambda_reg), float(temperature),
-                engine._ptr(terms), engine._ptr(loss), engine._ptr(grads), None,
-                engine._stream(dev)), "lgcn_ssm_loss_indexed")
+                engine._ptr(cand), engine._ptr(item_q), B, M, d, float(lambda_reg),
+                float(temperature), engine._ptr(terms), engine._ptr(loss), engine._ptr(grads),
+                None, engine._stream(dev)), "lgcn_ssm_loss_indexed_q")
         ctx.save_for_backward(grads, users, pos, cand)
         ctx.graph, ctx.K, ctx.hub_threshold = graph, K, hub_threshold
         ctx.sizes, ctx.n_e0 = sizes, n_e0
@@ -495,7 +498,7 @@ class SsmStepFunction(torch.autograd.Function):
                                               stream), "lgcn_rows_clear")
             ws.dirty = False
         blocks = tuple(torch.split(g0, sizes, 0))
-        return (None,) * 9 + blocks + ((gi,) if n_e0 == 1 else ())
+        return (None,) * 10 + blocks + ((gi,) if n_e0 == 1 else ())
 
 
 class InBatchStepFunction(torch.autograd.Function):
@@ -646,7 +649,7 @@ def _cpu_loss(tables, users, pos, neg, lambda_reg, item_brand, brand_loss_weight
 
 def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, item_brand=None,
              brand_loss_weight=0.1, negatives="hardest", return_negatives=False,
-             temperature=1.0):
+             temperature=1.0, neg_log_q=None):
     """The loss of one BPR batch (main.py:495-522) as a tensor whose
     `.backward()` leaves exactly the parameter `.grad`s main.py's route leaves:
 
@@ -697,6 +700,13 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
           With item_brand (and a weight != 0) it raises LgcnError before any launch: the brand
           term has no softmax form here. On a CPU adjacency the torch expression runs and a
           candidate out of range raises LgcnError.
+          neg_log_q (sampler.neg_log_q(): a contiguous float32 [num_items] tensor on the
+          adjacency's device, else LgcnError before any launch) is the logQ correction of
+          negatives drawn with probability Q: the logits become <u, i> / temperature -
+          neg_log_q[i] for the positive and every candidate (lgcn_ssm_loss_indexed_q), still
+          bitwise the gathered route through loss.ssm_loss_reg(q_pos=neg_log_q[pos],
+          q_neg=neg_log_q[neg]). It belongs to this mode alone: with another, or with a 1-D
+          neg, it raises ValueError ("hardest" and "all" train on weighted candidates as given).
     Any other value raises ValueError. return_negatives=True returns (loss, neg_used), the int64
     negatives the loss ran on: [B] for "hardest" (and for a 1-D neg, neg itself), [B*M] for "all",
     neg as given for "softmax". With a 1-D neg neither negatives nor temperature is looked at.
@@ -716,6 +726,11 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
     if many and negatives not in ("hardest", "all", "softmax"):
         raise ValueError(f"bpr_step: negatives={negatives!r} ('hardest', 'all' or 'softmax')")
     softmax = many and negatives == "softmax"
+    if neg_log_q is not None:
+        if not softmax:
+            raise ValueError("bpr_step: neg_log_q belongs to a [B, M] neg with "
+                             "negatives='softmax'")
+        _check_item_log_q(neg_log_q, I, adj.device, "bpr_step: neg_log_q")
     if softmax:
         temperature = _check_temperature(temperature, "bpr_step")
         if brand:
@@ -739,8 +754,10 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
             fu, fi, _, u0, i0 = tables
             B, M = neg.shape
             flat = neg.reshape(-1)
+            q = {} if neg_log_q is None else {"q_pos": neg_log_q[pos],
+                                              "q_neg": neg_log_q[flat].view(B, M)}
             loss = ssm_loss_torch(fu[users], fi[pos], fi[flat].view(B, M, -1), u0[users], i0[pos],
-                                  i0[flat].view(B, M, -1), lambda_reg, temperature)
+                                  i0[flat].view(B, M, -1), lambda_reg, temperature, **q)
             return (loss, neg) if return_negatives else loss
         if many:
             neg, found = select_hardest_torch(tables[0], tables[1], users, neg)
@@ -760,8 +777,8 @@ def bpr_step(model, adj, users, pos, neg, lambda_reg, check_indices=False, *, it
     graph = engine.graph_from_coo(adj, sides=engine.segment_sides(tensors[:3]))
     if softmax:
         loss = SsmStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
-                                     float(lambda_reg), temperature, users, pos, neg, n_e0,
-                                     *tensors)
+                                     float(lambda_reg), temperature, users, pos, neg, neg_log_q,
+                                     n_e0, *tensors)
         return (loss, neg) if return_negatives else loss
     if brand:
         out = BprBrandStepFunction.apply(graph, model.n_layers, engine.hub_threshold_from_env(),
@@ -818,15 +835,15 @@ def _check_positives(positives, num_users, device):
     return rowptr, items
 
 
-def _check_item_log_q(q, num_items, device):
+def _check_item_log_q(q, num_items, device, what="inbatch_step: item_log_q"):
     if not torch.is_tensor(q) or q.dtype != torch.float32:
-        raise engine.LgcnError("inbatch_step: item_log_q must be a float32 tensor, got "
+        raise engine.LgcnError(f"{what} must be a float32 tensor, got "
                                f"{getattr(q, 'dtype', type(q))}")
     if q.dim() != 1 or int(q.shape[0]) != num_items or not q.is_contiguous():
-        raise engine.LgcnError(f"inbatch_step: item_log_q must be a contiguous 1-D tensor of "
+        raise engine.LgcnError(f"{what} must be a contiguous 1-D tensor of "
                                f"{num_items} entries, got {tuple(q.shape)}")
     if q.device != device:
-        raise engine.LgcnError(f"inbatch_step: item_log_q on {q.device}, adjacency on {device}")
+        raise engine.LgcnError(f"{what} on {q.device}, adjacency on {device}")
 
 
 def inbatch_step(model, adj, users, pos, lambda_reg, temperature=1.0, *, positives=None,
@@ -895,7 +912,7 @@ def inbatch_step(model, adj, users, pos, lambda_reg, temperature=1.0, *, positiv
 
 def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
               item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
-              temperature=1.0, *, mask_positives=False, log_q=False):
+              temperature=1.0, *, mask_positives=False, log_q=False, neg_log_q=False):
     """One training epoch (main.py:488-531) that never leaves the device: the sampler draws the
     epoch's (user, positive, negative) triples in one launch (sampler.BprSampler.epoch), then per
     batch
@@ -915,7 +932,10 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     n_neg (None = the epoch above; an integer in [1, 64]) is passed to sampler.epoch: the draw
     holds n_neg candidate negatives per sample and every batch's neg is [batch, n_neg]; negatives
     ("hardest", "all" or "softmax") is bpr_step's and says what the step does with them;
-    temperature is the softmax step's.
+    temperature is the softmax step's. neg_log_q=True (with an integer n_neg and
+    negatives="softmax", else ValueError) passes sampler.neg_log_q() to every step as its
+    `neg_log_q`: the logQ correction that matches the sampler's draw, what a sampler built with
+    weights needs for an unbiased softmax.
 
     negatives="in_batch" (with n_neg=None; an integer n_neg raises ValueError): every batch runs
     model.inbatch_step(adj, users, pos, lambda_reg, temperature) — the in-batch softmax, a
@@ -929,6 +949,9 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
     in_batch = negatives == "in_batch"
     if (mask_positives or log_q) and not in_batch:
         raise ValueError("bpr_epoch: mask_positives and log_q belong to negatives='in_batch'")
+    if neg_log_q and (n_neg is None or negatives != "softmax"):
+        raise ValueError("bpr_epoch: neg_log_q belongs to an integer n_neg with "
+                         "negatives='softmax'")
     if in_batch:
         if n_neg is not None:
             raise ValueError("bpr_epoch: negatives='in_batch' draws no negatives (n_neg must be "
@@ -960,6 +983,8 @@ def bpr_epoch(model, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shu
         raise engine.LgcnError("bpr_epoch: a user has every item as a positive (no negative to "
                                "draw); the CPU route cannot skip the sample")
     many = {} if n_neg is None else {"negatives": negatives, "temperature": temperature}
+    if neg_log_q:
+        many["neg_log_q"] = sampler.neg_log_q()
     losses = []
     for users, pos, neg in batches:
         optimizer.zero_grad()

@@ -862,6 +862,39 @@ int lgcn_bpr_sample_multi(const int32_t* inter_user, const int32_t* inter_item, 
                           int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_unsampled,
                           void* stream);
 
+/* lgcn_bpr_sample_multi with negatives drawn in proportion to integer item weights w[i] in
+ * [0, 2^24] (popularity^alpha, quantised), given as two device int64 tables:
+ *  - item_cumw [n_items + 1]: the exclusive prefix sum of w; W = item_cumw[n_items].
+ *  - pos_cumw [n_pos + 1]: the exclusive prefix sum of w[pos_items[.]] over the whole positive
+ *    CSR, aligned with pos_rowptr: with beg = pos_rowptr[u], end = pos_rowptr[u + 1], a user's
+ *    prefix is pw[t] = pos_cumw[beg + t] - pos_cumw[beg], t in [0, deg], and pos_cumw[end] -
+ *    pos_cumw[beg] the weight of all its positives. The totals stay below 2^55.
+ * The draw of interaction idx, ordinal m: r64 is lgcn_bpr_sample_multi's (Philox4x32-10, counter
+ * (idx_lo32, idx_hi32, epoch, m), key = seed), then
+ *   W_free = W - (pos_cumw[end] - pos_cumw[beg])   <= 0: neg = -1 in all n_neg entries, and
+ *                                                  *n_unsampled rises once for the slot
+ *   r   = the high 64 bits of r64 * W_free
+ *   t*  = #{t in [0, deg) : item_cumw[L[t]] - pw[t] <= r}   (an upper-bound binary search: the
+ *         free weight below L[t] is non-decreasing in t)
+ *   r'  = r + pw[t*]
+ *   neg = (the first k in [0, n_items] with item_cumw[k] > r') - 1   (upper-bound binary search)
+ * r is a position in the concatenated weights of the user's free items, r' the same position in
+ * the weights of all items: a free item i is drawn with probability w[i] / W_free up to the 2^-64
+ * granularity of the range reduction, a positive or a zero-weight item never. A pure function of
+ * (seed, epoch, idx, m, the user's list, the weights): no alias table, no rejection loop. With
+ * every w[i] = 1 it is lgcn_bpr_sample_multi's draw bit for bit (item_cumw[k] = k, pw[t] = t).
+ * Memory safety, for any table contents: an L[t] outside [0, n_items) is not used as an index (it
+ * counts as "greater than r"); a result outside [0, n_items) is written as -1; pos_rowptr must be
+ * a CSR over pos_items and pos_cumw. Slots out of range are lgcn_bpr_sample_multi's. Refused on
+ * the host as lgcn_bpr_sample_multi refuses, in its order, NULL tables with the NULL pointers. */
+int lgcn_bpr_sample_weighted(const int32_t* inter_user, const int32_t* inter_item,
+                             int64_t n_inter, const int64_t* order, int64_t first, int64_t count,
+                             const int32_t* pos_rowptr, const int32_t* pos_items,
+                             const int64_t* pos_cumw, const int64_t* item_cumw, int64_t n_users,
+                             int64_t n_items, uint64_t seed, uint32_t epoch, int32_t n_neg,
+                             int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_unsampled,
+                             void* stream);
+
 /* Dynamic negative sampling: per sample the hardest of n_neg candidate negatives, neg_out[b] =
  * the candidate the current tables score highest for users[b] (cand: device int64 [B x n_neg]
  * row-major, e.g. lgcn_bpr_sample_multi's neg; fu / fi: the final user / item tables).
@@ -936,6 +969,28 @@ int lgcn_ssm_loss_indexed(const float* fu, int64_t ld_fu, const float* fi, int64
                           const int64_t* pos, const int64_t* cand, int32_t B, int32_t M,
                           int32_t d, float lambda, float temperature, float* terms, float* loss,
                           float* grads, float* coef, void* stream);
+
+/* The two above with a logQ correction of the logits (negatives drawn with probability Q, e.g.
+ * lgcn_bpr_sample_weighted's w[i] / W): z_0 = fp32(fp32(<u,p> * it) - q_0) and z_m =
+ * fp32(fp32(<u,n_m> * it) - q_m), lgcn_inbatch_loss's form; q enters the logits only, every other
+ * formula, order and layout is lgcn_ssm_loss's. Gathered: q_pos float32 [B], q_neg [B x M] (the
+ * candidate's by ordinal b * M + m); indexed: item_q [n_items], q_0 = item_q[pos[b]], q_m =
+ * item_q[cand[b][m]] — bitwise the gathered form on those values (one body). A q pointer may be
+ * NULL: no correction of that term; with every q NULL the subtraction is skipped and these are
+ * lgcn_ssm_loss / lgcn_ssm_loss_indexed, which call them so. q of a skipped sample or of an
+ * invalid candidate is not read. */
+int lgcn_ssm_loss_q(const float* u, int64_t ldu, const float* p, int64_t ldp, const float* n,
+                    int64_t ldn, const float* u0, int64_t ldu0, const float* p0, int64_t ldp0,
+                    const float* n0, int64_t ldn0, const uint8_t* valid, const float* q_pos,
+                    const float* q_neg, int32_t B, int32_t M, int32_t d, float lambda,
+                    float temperature, float* terms, float* loss, float* grads, float* coef,
+                    void* stream);
+int lgcn_ssm_loss_indexed_q(const float* fu, int64_t ld_fu, const float* fi, int64_t ld_fi,
+                            const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                            int64_t n_users, int64_t n_items, const int64_t* users,
+                            const int64_t* pos, const int64_t* cand, const float* item_q,
+                            int32_t B, int32_t M, int32_t d, float lambda, float temperature,
+                            float* terms, float* loss, float* grads, float* coef, void* stream);
 
 /* The (2+M)B destination keys of that batch's gradient rows, keys int64 in grads' row order:
  * lgcn_bpr_keys' numbering (2 * row, bit 0 set for a candidate's row). "None" =

@@ -114,16 +114,18 @@ class LightGCN(nn.Module):
 
     def bpr_step(self, adj, users, pos, neg, lambda_reg, *, item_brand=None,
                  brand_loss_weight=0.1, negatives="hardest", return_negatives=False,
-                 temperature=1.0):
+                 temperature=1.0, neg_log_q=None):
         """The BPR + L2 loss of one batch (main.py:495-522) in one call that keeps the batch
         indices: `.backward()` leaves the `.grad`s of the hand-written route, to the bit
         (train.bpr_step). item_brand (data.item_brand_map) adds the brand loss. A [B, M] neg
         holds M candidate negatives per sample: negatives="hardest" trains on the one the model
         scores highest, chosen inside the step; "all" on every pair; "softmax" on the
-        sampled-softmax loss over all M with logits divided by `temperature`."""
+        sampled-softmax loss over all M with logits divided by `temperature`, less `neg_log_q`
+        (sampler.neg_log_q(), the logQ correction of weighted negatives) when given."""
         return train.bpr_step(self, adj, users, pos, neg, lambda_reg, item_brand=item_brand,
                               brand_loss_weight=brand_loss_weight, negatives=negatives,
-                              return_negatives=return_negatives, temperature=temperature)
+                              return_negatives=return_negatives, temperature=temperature,
+                              neg_log_q=neg_log_q)
 
     def inbatch_step(self, adj, users, pos, lambda_reg, temperature=1.0, *, positives=None,
                      item_log_q=None, check_indices=False):
@@ -137,18 +139,20 @@ class LightGCN(nn.Module):
 
     def bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch, shuffle=True,
                   item_brand=None, brand_loss_weight=0.1, n_neg=None, negatives="hardest",
-                  temperature=1.0, *, mask_positives=False, log_q=False):
+                  temperature=1.0, *, mask_positives=False, log_q=False, neg_log_q=False):
         """One epoch of bpr_step batches over one device-side draw of the sampler
         (train.bpr_epoch): the per-batch losses as one tensor, no host read-back in the loop.
         `gcn_recommendation_amd.optim.Adam` as the optimizer keeps the whole step inside the
         engine, with torch.optim.Adam's bits. n_neg = M draws M candidate negatives per sample
         for bpr_step's `negatives` mode; negatives="in_batch" (n_neg=None) runs inbatch_step on
-        every batch, with mask_positives / log_q taken from the sampler."""
+        every batch, with mask_positives / log_q taken from the sampler; neg_log_q=True gives
+        the "softmax" steps the sampler's neg_log_q()."""
         return train.bpr_epoch(self, adj, sampler, optimizer, lambda_reg, batch_size, epoch,
                                shuffle=shuffle, item_brand=item_brand,
                                brand_loss_weight=brand_loss_weight, n_neg=n_neg,
                                negatives=negatives, temperature=temperature,
-                               mask_positives=mask_positives, log_q=log_q)
+                               mask_positives=mask_positives, log_q=log_q,
+                               neg_log_q=neg_log_q)
 
     def evaluate_ranks(self, adj, evaluator, eval_users, eval_items, ks=(20,)):
         """Recall@k / NDCG@k for every k of `ks` and MRR from one device-side pass

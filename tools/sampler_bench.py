@@ -21,6 +21,11 @@ against one training step of the commit before the sampler (profiles/bpr_step_c3
 shuffled order) beside the one-negative draw, the variants interleaved rep by rep, and compares
 the first slots of each with the numpy path.
 
+--weighted [--alpha A] [--n-neg M ...] times only the device draw of a sampler built with
+weights="popularity" (lgcn_bpr_sample_weighted, count^A weights) beside the uniform sampler's, with
+one negative and with each M (default 16), shuffled order, the variants interleaved rep by rep, and
+compares the first slots of each weighted draw with the numpy twin.
+
 One process, so the three figures come from one machine in one run; it holds the GPU for the
 whole of it and is therefore started under a time limit of its own, as every GPU step is.
 """
@@ -111,6 +116,59 @@ def multi_neg(args, s, users, items, U, I, E, epoch, cfg):
     print(json.dumps(result), flush=True)
 
 
+def weighted(args, s, users, items, U, I, E, epoch, cfg):
+    """--weighted: the whole-epoch shuffled device draw of the uniform sampler and of one built
+    with weights="popularity", with one negative and with each M of --n-neg, the variants
+    interleaved rep by rep; the first --check slots of every weighted draw are compared with the
+    numpy twin."""
+    t0 = time.perf_counter()
+    sw = sampler.BprSampler(users, items, U, I, s.device, seed=args.seed, weights="popularity",
+                            alpha=args.alpha)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
+    perm = s.permutation(epoch)
+    variants = [(kind, M) for M in [None] + list(args.n_neg or [16])
+                for kind in ("uniform", "weighted")]
+    check = min(args.check, E, 100_000)
+    order = perm[:check].cpu().numpy()
+    c = sampler.BprSampler(users, items, U, I, "cpu", seed=args.seed, weights=sw.item_weights)
+    unsampled = {}
+    for kind, M in variants:   # warm-up and the comparison
+        smp = sw if kind == "weighted" else s
+        got = smp.draw(epoch, perm, n_neg=M)[2][:check].cpu().numpy()
+        unsampled[kind] = int(smp.unsampled.item())
+        if kind == "weighted":
+            want = sampler.sample_numpy(c._user, c._item, order, 0, check, c._rowptr, c._pos_items,
+                                        U, I, args.seed, epoch, n_neg=M, cumw=c._cumw)[2]
+            assert np.array_equal(got, want), f"weighted draw differs from numpy at n_neg={M}"
+        del got
+    times = {v: [] for v in variants}
+    for _ in range(args.reps):
+        for kind, M in variants:
+            smp = sw if kind == "weighted" else s
+            times[(kind, M)] += device_ms(lambda: smp.draw(epoch, perm, n_neg=M), 1)
+
+    def key(kind, M):
+        return f"{kind}_" + ("one_negative" if M is None else f"n_neg_{M}")
+
+    w = sw.item_weights
+    result = {
+        "config": cfg["name"], "interactions": E, "users": U, "items": I, "reps": args.reps,
+        "alpha": args.alpha, "weighted_sampler_build_s": round(build_s, 2),
+        "weights": {"zero": int((w == 0).sum()), "one": int((w == 1).sum()), "total": int(w.sum()),
+                    "table_bytes": int((I + 1) * 8 + sw._cumw[0].numel() * 8)},
+        "unsampled": unsampled,
+        "device_draw_ms_shuffled": {key(*v): round(float(np.median(t)), 3)
+                                    for v, t in times.items()},
+        "device_draw_ms_all": {key(*v): [round(x, 3) for x in t] for v, t in times.items()},
+        "weighted_equals_numpy_first_slots": check,
+        "what": ("one whole-epoch BprSampler.draw(order=randperm, n_neg=M) between events, uniform "
+                 "and weights='popularity' samplers and every M interleaved rep by rep, median of "
+                 "reps; the output allocation (torch.empty) is inside the timed region"),
+    }
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3", choices=sorted(bench.CONFIGS))
@@ -121,6 +179,10 @@ def main():
     ap.add_argument("--n-neg", type=int, nargs="+", default=None, metavar="M",
                     help="time only the device draw with M negatives per sample (several values: "
                          "interleaved), one negative beside them")
+    ap.add_argument("--weighted", action="store_true",
+                    help="time only the device draw of a weights='popularity' sampler beside the "
+                         "uniform one, with one negative and with each M of --n-neg (default 16)")
+    ap.add_argument("--alpha", type=float, default=0.75, help="exponent of --weighted's counts")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("sampler_bench: needs a HIP device")
@@ -139,6 +201,9 @@ def main():
     build_s = time.perf_counter() - t0
     bench.log(f"[sampler_bench] device sampler built in {build_s:.1f}s")
     epoch = 1
+    if args.weighted:
+        weighted(args, s, users, items, U, I, E, epoch, cfg)
+        return
     if args.n_neg:
         multi_neg(args, s, users, items, U, I, E, epoch, cfg)
         return
